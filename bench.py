@@ -21,8 +21,19 @@ compile() (searched, or --strategy dp for the data-parallel baseline).
 Each timed step = forward + loss + backward + gradient all-reduce + Adam
 update over all parameters.  Rank 0 prints ONE JSON line.
 
+A plain run does only what the headline needs: set-up, W warm-up steps, the
+K timed steps, the line.  --dump-outputs DIR also writes what the last timed
+step left with its caller -- the parameters after the update (large ones as
+a fixed seeded sample), the metrics buffer and the mean loss -- as
+DIR/params.npy, metrics.npy (float32) and loss.npy (float64); the same
+arguments give the same inputs in every run, so two builds can be compared
+array for array (_dump_outputs).  Everything else the benchmark
+measures is behind --full: the memory plan against a separately measured
+step peak, and with N > 1 the collectives' calibration, the data-parallel
+reference run and the AE protocol described below.
+
 Speedup over data parallelism (the reference's Unity-vs-DP protocol,
-scripts/osdi22ae/*.sh): with N > 1 and the searched strategy, the line
+scripts/osdi22ae/*.sh): with --full, N > 1 and the searched strategy, the line
 carries ``speedup_over_dp`` — 1.0 when the search itself chose pure data
 parallelism, else the searched samples/s over a data-parallel run of the
 same model and batch measured right after (same K / W, outside the headline
@@ -58,6 +69,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the memory plan against a measured step peak "
+                         "and, with N > 1, the collectives' calibration, the data-parallel reference run and the AE "
+                         "protocol (all outside the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left with its caller as DIR/<name>.npy: "
+                         "params (every parameter, large ones as a fixed seeded sample), metrics, loss; under 64 MB "
+                         "in all")
     ap.add_argument("--batch-per-gpu", type=int, default=0, help="default: 128 (BERT), 512 (ResNet-50), 1024 (DLRM), "
                                                                    "32 (GPT-3 medium) -- 64 / 256 / 16 before round 6; sized "
                                                                    "for 288 GB of HBM per GPU (profiles/r6/g40_*, "
@@ -67,10 +86,10 @@ def main():
                     choices=["bert-large", "bert-base", "resnet50", "resnext50", "inception-v3", "dlrm",
                              "gpt3-medium"])
     ap.add_argument("--no-calibrate", action="store_true",
-                    help="N > 1: skip timing the step's RCCL collectives (cost-model calibration, outside the "
+                    help="--full, N > 1: skip timing the step's RCCL collectives (cost-model calibration, outside the "
                          "timed region)")
     ap.add_argument("--ae", action="store_true",
-                    help="(default at N > 1 for BERT) also run the reference's OSDI'22 AE BERT protocol "
+                    help="(default with --full at N > 1 for BERT) also run the reference's OSDI'22 AE BERT protocol "
                          "(scripts/osdi22ae/bert.sh: 12 layers, hidden 1024, 16 heads, seq 512, global batch 8, "
                          "--budget 30) searched vs data parallel, reported as config.ae_bert (outside the headline "
                          "timed region)")
@@ -96,6 +115,8 @@ def main():
                     help="replay the training step from a hipGraph (1) or run eagerly (0); default 1: one graph "
                          "on a single GPU, graph segments cut at every RCCL collective across ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     os.environ["FF_GEMM"] = args.gemm
     t_start = time.time()
@@ -114,10 +135,13 @@ def main():
 
     res = runner(args, world, rank, only_dp=args.strategy == "dp")
     dist_world, backend = _check_world(res["ex"], args.gpus)
+    if args.dump_outputs:
+        _dump_outputs(res["ex"], args.dump_outputs, rank)
+    # --full at N > 1: the multi-rank flow after the headline -- calibration,
+    # the watchdog, the DP reference and the AE protocol.
     # FF_BENCH_REHEARSE_MULTI=1 (with FF_DIST_WORLD1=1: RCCL at world 1) runs
-    # the multi-rank flow after the headline -- calibration, the watchdog,
-    # the DP reference and the AE protocol -- on one GPU
-    multi = world > 1 or os.environ.get("FF_BENCH_REHEARSE_MULTI") == "1"
+    # it on one GPU
+    multi = args.full and (world > 1 or os.environ.get("FF_BENCH_REHEARSE_MULTI") == "1")
     if multi and not args.no_calibrate:
         # after the timed steps: the collectives the step issued, timed at its
         # own message sizes on this process group, fitted into the cost model;
@@ -324,6 +348,59 @@ def _release(res):
                   f"reserved {torch.cuda.memory_reserved() / 1e9:.2f} GB", file=sys.stderr, flush=True)
 
 
+_DUMP_BUDGET_BYTES = 48 << 20   # of the 64 MB a dump may take
+
+
+def _dump_outputs(ex, out_dir: str, rank: int):
+    """--dump-outputs: what the last timed step left with its caller, as
+    DIR/<name>.npy --
+      params   every parameter after the update (the full logical fp32
+               weight), flattened and concatenated in parameter order;
+      metrics  the metrics buffer the steps accumulated into (loss sum,
+               correct predictions, count);
+      loss     the mean loss those give (the line's final_loss, float64).
+    A parameter above the per-parameter cap enters as a sample at fixed
+    positions drawn from a seed that depends only on its name and size, so
+    every run samples alike.  The gradients of the last step are left out on
+    purpose: this workload (random labels, Adam from a random start) amplifies
+    the rounding differences between two runs of ONE build -- other GEMM
+    kernels picked by the timing-based autotuner, floating-point atomics -- to
+    ~30 % of a gradient's norm after 25 steps (BERT-large, measured), so they
+    cannot tell two builds apart; the same two runs differ by 2e-4 of the
+    norm of ``params`` (at most 1e-3 in one element) and 1e-5 of the loss.
+    Every rank takes part (the gather across ranks is collective); rank 0
+    writes."""
+    import zlib
+
+    import numpy as np
+    import torch
+
+    if ex.cfg.device.type == "cuda":
+        torch.cuda.synchronize()
+    names = ex.parameter_names()
+    cap = max(256, min(65536, _DUMP_BUDGET_BYTES // 4 // max(1, len(names))))
+    pieces = []
+    for name in names:
+        flat = ex.get_parameter(name).detach().reshape(-1).to(torch.float32)
+        if flat.numel() > cap:
+            rng = np.random.default_rng(zlib.crc32(f"{name}:{flat.numel()}".encode()))
+            idx = np.sort(rng.integers(0, flat.numel(), size=cap, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        if rank == 0:
+            pieces.append(flat.cpu().numpy())
+    loss = ex.perf_metrics().loss
+    if rank != 0:
+        return
+    out = {"params": np.concatenate(pieces) if pieces else np.zeros(0, np.float32),
+           "metrics": ex.metrics_buf.detach().to(torch.float32).cpu().numpy(),
+           "loss": np.array([loss], dtype=np.float64)}
+    if sum(a.nbytes for a in out.values()) > (64 << 20):
+        raise RuntimeError("--dump-outputs: above the 64 MB limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
 def _memory_record(model, ex, world, bytes_per_param=16.0):
     """This rank's liveness memory plan of the step (csrc/ffcore/src/
     memory_plan.cc) next to the allocator's measured peak, GB."""
@@ -413,16 +490,17 @@ def _time_steps(args, ex, feeds, labels, global_batch, model=None, bytes_per_par
 
     phase("compiled")
     if dev.type == "cuda" and not args.profile:
-        # the step's own memory peak: one eager step to settle the autotuner
-        # and the workspaces, then one measured from a reset peak counter
+        # one eager step to settle the autotuner and the workspaces
         ex.train_step(feeds, labels)
         phase("eager step 1")
-        torch.cuda.synchronize()
-        torch.cuda.reset_peak_memory_stats(dev)
-        ex.train_step(feeds, labels)
-        torch.cuda.synchronize()
-        ex._ff_step_peak = torch.cuda.max_memory_allocated(dev)
-        phase("eager step 2")
+        if args.full:
+            # the step's own memory peak: one more, measured from a reset peak counter
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats(dev)
+            ex.train_step(feeds, labels)
+            torch.cuda.synchronize()
+            ex._ff_step_peak = torch.cuda.max_memory_allocated(dev)
+            phase("eager step 2")
     graphed = False
     use_graph = args.graph if args.graph >= 0 else 1
     if use_graph and dev.type == "cuda" and not args.profile:
@@ -534,7 +612,7 @@ def _run_bert(args, world, rank, only_dp: bool):
         "gemm_choices": dict(collections.Counter(gemm_choices().values())),
         "tokens_per_sec": round(t["value"] * args.seq, 1),
         "final_loss": round(pm.loss, 4),
-        "memory": _memory_record(model, ex, world),
+        "memory": _memory_record(model, ex, world) if args.full else None,
         "search": _search_record(model, world),
     }
     prof = None
@@ -801,7 +879,7 @@ def _run_zoo(args, world, rank, only_dp: bool):
             "native_replay": getattr(ex, "native_replay", None), "final_loss": round(pm.loss, 4),
             # resident bytes per parameter: fp32 master + bf16 copy + gradient
             # + optimizer state (Adam m, v: 16; SGD momentum: 14; plain SGD: 10)
-            "memory": _memory_record(model, ex, world, bpp),
+            "memory": _memory_record(model, ex, world, bpp) if args.full else None,
             "search": _search_record(model, world)}
     conf.update(extra)
     if zname == "gpt":

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ARGS = ["--model", "bert-base", "--layers", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2",
         "--seq", "64", "--no-dp-compare", "--no-ae"]
@@ -33,6 +35,37 @@ def test_bench_self_launches_n_ranks():
     assert r["config"]["global_batch"] == 4 and r["steps"] == 2 and r["warmup"] == 1
 
 
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(tmp_path):
+    """A plain run prints the headline line without the --full extras, and
+    --dump-outputs writes the last step's parameters / metrics / loss as .npy
+    under 64 MB, identical from run to run on the CPU (same inputs)."""
+    import numpy as np
+    dumps = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + ARGS
+                           + ["--dump-outputs", str(d)], env=_env(), capture_output=True, text=True, timeout=600,
+                           cwd="/tmp")
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, p.stdout
+        r = lines[0]
+        assert r["metric"] == "samples_per_sec_whole_node" and r["unit"] == "samples/s" and r["higher_is_better"]
+        assert r["steps"] == 2 and r["ms_per_step"] > 0 and r["dtype"] == "bf16"
+        assert r["value"] == pytest.approx(r["config"]["global_batch"] * 1000.0 / r["ms_per_step"], rel=1e-2)
+        assert r["config"]["memory"] is None and "comm_calibration" not in r["config"]
+        files = sorted(os.listdir(d))
+        assert files == ["loss.npy", "metrics.npy", "params.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        dumps.append({f: np.load(d / f) for f in files})
+        assert float(dumps[-1]["loss.npy"][0]) == pytest.approx(r["config"]["final_loss"], abs=1e-4)
+    a, b = dumps
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and np.isfinite(a[f]).all(), f
+        np.testing.assert_array_equal(a[f], b[f], err_msg=f)
+    assert a["params.npy"].size > 100000 and np.abs(a["params.npy"]).max() > 0
+
+
 def test_bench_refuses_world_mismatch():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + ARGS,
                        env=_env(WORLD_SIZE="1", RANK="0"), capture_output=True, text=True, timeout=300, cwd="/tmp")
@@ -42,12 +75,12 @@ def test_bench_refuses_world_mismatch():
 
 
 def test_bench_multi_rank_emits_comm_calibration_and_ae():
-    """N > 1: the JSON line carries the measured collectives at the step's
-    message sizes against the cost model before / after calibration, the
-    simulator's predicted step beside the measured one, and (--ae) the
+    """--full, N > 1: the JSON line carries the measured collectives at the
+    step's message sizes against the cost model before / after calibration,
+    the simulator's predicted step beside the measured one, and (--ae) the
     OSDI'22 AE BERT protocol's searched-vs-DP ratio."""
     args = ["--model", "bert-base", "--layers", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2",
-            "--seq", "64", "--no-dp-compare"]
+            "--seq", "64", "--no-dp-compare", "--full"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args, env=_env(),
                        capture_output=True, text=True, timeout=900, cwd="/tmp")
     assert p.returncode == 0, p.stderr[-3000:]
@@ -66,11 +99,11 @@ def test_bench_multi_rank_emits_comm_calibration_and_ae():
 
 def test_bench_eight_ranks_reports_measured_speedups():
     """The driver's 8-GPU line, rehearsed on 8 gloo ranks: the AE protocol runs
-    by default at N > 1 (no --ae), and the line carries the measured
-    searched-vs-DP ratios (headline and AE config), the collectives'
+    by default with --full at N > 1 (no --ae), and the line carries the
+    measured searched-vs-DP ratios (headline and AE config), the collectives'
     calibration and what the search did."""
     args = ["--model", "bert-base", "--layers", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2",
-            "--seq", "64"]
+            "--seq", "64", "--full"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8"] + args,
                        env=_env(OMP_NUM_THREADS="1"), capture_output=True, text=True, timeout=1500, cwd="/tmp")
     assert p.returncode == 0, p.stderr[-3000:]
@@ -96,7 +129,7 @@ def test_bench_deadline_keeps_the_headline():
     at --deadline-s is abandoned: rank 0 prints the line with what finished
     and every rank exits 0 (a hang there never costs the measured number)."""
     args = ["--model", "bert-base", "--layers", "2", "--steps", "2", "--warmup", "1", "--batch-per-gpu", "2",
-            "--seq", "64", "--no-calibrate", "--deadline-s", "1"]
+            "--seq", "64", "--no-calibrate", "--deadline-s", "1", "--full"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2"] + args, env=_env(),
                        capture_output=True, text=True, timeout=900, cwd="/tmp")
     assert p.returncode == 0, p.stderr[-3000:]

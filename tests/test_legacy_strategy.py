@@ -8,13 +8,13 @@ import os
 import pytest
 
 import dist_models as M
+import golden_files as G
 from dist_util import assert_params_close, run_distributed, run_single
 from flexflow_train_amd.search import legacy_strategy as L
 
-REF = "/root/reference/examples/cpp/DLRM/strategies"
+REF = G.DLRM_STRATEGIES
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted")
 @pytest.mark.parametrize("fname", ["dlrm_strategy_8embs_8gpus.pb", "dlrm_strategy_16embs_8gpus.pb",
                                    "dlrm_strategy_16embs_16gpus.pb"])
 def test_reference_pb_roundtrip(fname):
@@ -31,7 +31,6 @@ def _dlrm8(m):
                              mlp_bot=[8, 16, 16], mlp_top=[16, 16, 2]))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted")
 def test_lower_reference_dlrm_strategy():
     from flexflow_train_amd import _ffcore as C
     from flexflow_train_amd.core import FFConfig, FFModel

@@ -12,9 +12,10 @@ import subprocess
 
 import pytest
 
+import golden_files as G
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ASAN = os.path.join(ROOT, "bin", "asan")
-REF_SUBST = "/root/reference/substitutions"
 TOOLS = ("ffc-export-model-arch", "ffc-substitution-to-dot", "ffc-protobuf-to-json", "ffc-ffi-test",
          "ffc-runtime-c-test")
 ENV = dict(os.environ,
@@ -68,11 +69,10 @@ def test_c_runtime_api_under_sanitizers():
     assert "PASSED (0 failures)" in _run("ffc-runtime-c-test").stdout
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_SUBST, "graph_subst_3_v2.pb")), reason="no corpus")
 def test_rule_corpus_tools_under_sanitizers(tmp_path):
     out = str(tmp_path / "r.json")
-    _run("ffc-protobuf-to-json", os.path.join(REF_SUBST, "graph_subst_3_v2.pb"), out)
+    _run("ffc-protobuf-to-json", G.RULES_PB, out)
     assert len(json.load(open(out))["rule"]) == 640
-    path = os.path.join(REF_SUBST, "graph_subst_3_v2.json")
+    path = G.rules_json_file(tmp_path)
     assert "cluster_src" in _run("ffc-substitution-to-dot", path, "taso_rule_7").stdout
     assert len(_run("ffc-substitution-to-dot", path, "--list").stdout.strip().splitlines()) == 640

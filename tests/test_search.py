@@ -3,15 +3,13 @@ substitutions and search (CPU).  Mirrors the reference's compiler tests
 (lib/compiler/test/src/compiler/machine_mapping/*, allowed_machine_views.cc,
 series_parallel/*, lib/substitutions/test/*)."""
 import json
-import os
 
 import pytest
 
+import golden_files as G
 from flexflow_train_amd import _ffcore as C
 from flexflow_train_amd.core import ActiMode, DataType, FFConfig, FFModel
 from flexflow_train_amd.search import native
-
-REF_RULES = "/root/reference/substitutions/graph_subst_3_v2.json"
 
 
 def mlp_cg(batch=64, hidden=64, layers=3):
@@ -224,10 +222,8 @@ def test_substitution_column_parallel_recreates_weights():
     g.reinfer_shapes()
 
 
-@pytest.mark.skipif(not os.path.exists(REF_RULES), reason="reference rule corpus not present")
 def test_legacy_rule_corpus():
-    with open(REF_RULES) as f:
-        coll = C.load_legacy_rules(f.read())
+    coll = C.load_legacy_rules(G.rules_json_text())
     assert len(coll) == 640
     dot = coll.to_dot(0)
     assert dot.startswith("digraph") and "OP_PARTITION" in dot

@@ -8,15 +8,14 @@ by isomorphism), lib/compiler/src/unity_algorithm.cc:27-91 (best-first over
 every substitution at every match), substitutions/graph_subst_3_v2.json."""
 import collections
 import json
-import os
 
 import pytest
 
+import golden_files as G
 from flexflow_train_amd import _ffcore as C
 from flexflow_train_amd.core import ActiMode, DataType, FFConfig, FFModel
 from flexflow_train_amd.search import native, unity
 
-REF_RULES = "/root/reference/substitutions/graph_subst_3_v2.json"
 BUNDLED = unity.DEFAULT_RULES
 
 
@@ -41,16 +40,15 @@ def test_bundled_rule_set_covers_the_corpus():
     assert all(n.startswith("legacy_taso_rule_") for n in names)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_RULES), reason="reference rule corpus not present")
 def test_corpus_conversion_matches_bundled_and_explains_the_rest():
-    with open(REF_RULES) as f:
-        subs, skipped = C.load_substitutions(f.read())
+    corpus = G.rules_json_text()
+    subs, skipped = C.load_substitutions(corpus)
     assert len(subs) + len(skipped) == 640
     assert len(subs) == len(_bundled())
     # every rule left out uses an activation as a Linear weight (docs/TASO_RULES.md)
     for s in skipped:
         assert "weight" in s, s
-    coll = C.load_legacy_rules(open(REF_RULES).read())
+    coll = C.load_legacy_rules(corpus)
     why = [coll.conversion_failure(i) for i in range(len(coll))]
     assert sum(1 for w in why if w) == len(skipped) + sum(1 for s in subs if s.name.endswith("_rev"))
 
