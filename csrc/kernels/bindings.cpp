@@ -258,6 +258,43 @@ PYBIND11_MODULE(_ffkernels, m) {
                   uintptr_t st) {
     bmm_bf16(P(A), P(B), P(C), batch, M, N, K, lda, ldb, ldc, sA, sB, sC, ta, tb, alpha, beta, out_f32, S(st));
   });
+  m.def("grouped_gemm", [](int form, uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre,
+                           uintptr_t aux, uintptr_t offsets, uintptr_t tile_group, uintptr_t tile_row0,
+                           uintptr_t n_tiles, int El, int T, int M, int N, int K, int lda, int ldb, int ldc,
+                           int64_t sB, int64_t sC, int64_t sBias, int act, bool act_bwd, float beta, int out_f32,
+                           uintptr_t st) {
+    GroupedGemmParams p;
+    p.form = form; p.A = P(A); p.B = P(B); p.C = P(C); p.bias = P(bias); p.pre = P(pre); p.aux = P(aux);
+    p.offsets = static_cast<const int*>(P(offsets)); p.tile_group = static_cast<const int*>(P(tile_group));
+    p.tile_row0 = static_cast<const int*>(P(tile_row0)); p.n_tiles = static_cast<const int*>(P(n_tiles));
+    p.El = El; p.T = T; p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.sB = sB; p.sC = sC; p.sBias = sBias; p.act = act; p.act_bwd = act_bwd; p.beta = beta; p.out_f32 = out_f32;
+    grouped_gemm_bf16(p, S(st));
+  });
+  m.def("moe_route_ws", &moe_route_ws);
+  m.def("moe_route", [](uintptr_t ids, int64_t Pn, int e0, int El, uintptr_t offsets, uintptr_t perm, uintptr_t pos,
+                        uintptr_t tile_group, uintptr_t tile_row0, uintptr_t n_tiles, int T, uintptr_t ws,
+                        uintptr_t st) {
+    auto I = [](uintptr_t p) { return reinterpret_cast<int*>(p); };
+    moe_route(I(ids), Pn, e0, El, I(offsets), I(perm), I(pos), I(tile_group), I(tile_row0), I(n_tiles), T, I(ws),
+              S(st));
+  });
+  m.def("moe_gather_rows", [](uintptr_t x, uintptr_t perm, uintptr_t scale, uintptr_t n_ptr, uintptr_t xs,
+                              int64_t Pn, int D, int k, uintptr_t st) {
+    moe_gather_rows(P(x), static_cast<const int*>(P(perm)), P(scale), static_cast<const int*>(P(n_ptr)), P(xs), Pn,
+                    D, k, S(st));
+  });
+  m.def("moe_combine", [](uintptr_t y, uintptr_t pos, uintptr_t gate, uintptr_t out, int64_t B, int k, int O,
+                          uintptr_t st) {
+    moe_combine(P(y), static_cast<const int*>(P(pos)), P(gate), P(out), B, k, O, S(st));
+  });
+  m.def("moe_dgate", [](uintptr_t dout, uintptr_t y, uintptr_t pos, uintptr_t dgate, int64_t B, int k, int O,
+                        uintptr_t st) {
+    moe_dgate(P(dout), P(y), static_cast<const int*>(P(pos)), F(dgate), B, k, O, S(st));
+  });
+  m.def("moe_segment_colsum", [](uintptr_t x, uintptr_t offsets, uintptr_t out, int El, int N, uintptr_t st) {
+    moe_segment_colsum(P(x), static_cast<const int*>(P(offsets)), F(out), El, N, S(st));
+  });
   m.def("gemmp", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre, uintptr_t aux,
                     uintptr_t dbias, int M, int N, int K, int lda, int ldb, int ldc, bool ta, bool tb, int act,
                     bool act_bwd, float alpha, float beta, int out_f32, int splits, uintptr_t ws, uintptr_t st,

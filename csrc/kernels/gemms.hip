@@ -17,6 +17,8 @@
 //     column per wave half), plain alpha / beta (bf16 or fp32 out) and split-K
 //     fp32 slabs (reduced by gemmp.hip's splitk_reduce).
 // Bijective XCD remap + grouped raster as gemm.hip.
+// The grouped (ragged) form at the end of the file runs the expert MLPs of a
+// mixture-of-experts block over row ranges kept on the device (moe.hip).
 #include <type_traits>
 
 #include "kernels.h"
@@ -88,6 +90,25 @@ struct SStager {
         src = P + static_cast<int64_t>(outer0 + r) * ld + k0 + ch * 8;
       } else {
         ok = outer0 + ch * 8 < n_outer;
+        src = P + static_cast<int64_t>(k0 + r) * ld + outer0 + ch * 8;
+      }
+      reg[i] = ok ? *reinterpret_cast<const bf16x8*>(src) : bf16x8{};
+    }
+  }
+  // as load, with the contraction index bounded too: chunks at or beyond k_hi
+  // enter as zeros (K tails, and the ragged row ranges of the grouped kernel)
+  __device__ __forceinline__ void load_k(const bf16* P, int ld, int outer0, int n_outer, int k0, int k_hi) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = threadIdx.x + SNT * i;
+      const int r = c >> 3, ch = c & 7;
+      bool ok;
+      const bf16* src;
+      if (KC) {
+        ok = outer0 + r < n_outer && k0 + ch * 8 < k_hi;
+        src = P + static_cast<int64_t>(outer0 + r) * ld + k0 + ch * 8;
+      } else {
+        ok = outer0 + ch * 8 < n_outer && k0 + r < k_hi;
         src = P + static_cast<int64_t>(k0 + r) * ld + outer0 + ch * 8;
       }
       reg[i] = ok ? *reinterpret_cast<const bf16x8*>(src) : bf16x8{};
@@ -241,7 +262,206 @@ __global__ __launch_bounds__(SNT) void gemms_kernel(GemmSArgs g) {
   }
 }
 
+// ---- grouped (ragged) form: the expert MLPs of ops/moe.py ------------------
+// Row blocks [offsets[e], offsets[e+1]) of A / C belong to group e, whose
+// weight is B + e * sB.  FORM 0 (NN): C[rows_e] = act(A[rows_e] B[e] + bias[e]);
+// FORM 1 (NT): C[rows_e] = A[rows_e] B[e]^T (* act'(aux)); both walk the
+// device-side row-tile map of moe_route (tile -> group, first row) and bound
+// the rows by the group's end.  FORM 2 (TN): C[e] = beta C[e] + A[rows_e]^T
+// B[rows_e]: the contraction runs over the group's rows, rows at and beyond
+// its end enter as zeros.
+enum GForm : int { gNN = 0, gNT = 1, gTN = 2 };
+
+struct GemmGArgs {
+  const bf16* A;
+  const bf16* B;
+  void* C;
+  const bf16* bias;
+  bf16* pre;
+  const bf16* aux;
+  const int* offsets;
+  const int* tile_group;
+  const int* tile_row0;
+  const int* n_tiles;
+  int T, M, N, K, lda, ldb, ldc;
+  int64_t sB, sC, sBias;
+  float beta;
+  int out_f32;
+};
+
+template <int FORM, int EPI, int ACT>
+__global__ __launch_bounds__(SNT) void gemmg_kernel(GemmGArgs g) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * SIMG];  // A0 B0 A1 B1
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int wm = wave & 1, wn = wave >> 1;
+
+  int e, m0, n0, m_hi, k_lo, k_hi;
+  if (FORM == gTN) {
+    e = blockIdx.z;
+    m0 = blockIdx.x * SM;
+    n0 = blockIdx.y * SN;
+    m_hi = g.M;
+    k_lo = g.offsets[e];
+    k_hi = g.offsets[e + 1];
+    if (k_hi <= k_lo && g.beta != 0.f) return;  // empty group, accumulate: C[e] stays
+  } else {
+    const int t = blockIdx.x % g.T;
+    if (t >= *g.n_tiles) return;  // the grid is sized by the static tile bound
+    e = g.tile_group[t];
+    m0 = g.tile_row0[t];
+    n0 = (blockIdx.x / g.T) * SN;
+    m_hi = g.offsets[e + 1];
+    k_lo = 0;
+    k_hi = g.K;
+  }
+  const bf16* A = g.A;
+  const bf16* B = g.B + (FORM == gTN ? 0 : e * g.sB);
+  constexpr bool AKC = FORM != gTN, BKC = FORM == gNT;
+  const int nk = (k_hi - k_lo + SK - 1) / SK;
+
+  SStager<AKC> sa;
+  SStager<BKC> sbs;
+  f32x16 acc = f32x16{};
+  sa.load_k(A, g.lda, m0, m_hi, k_lo, k_hi);
+  sbs.load_k(B, g.ldb, n0, g.N, k_lo, k_hi);
+  sa.store(smem);
+  sbs.store(smem + SIMG);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const unsigned char* Ai = smem + (kt & 1) * 2 * SIMG;
+    const unsigned char* Bi = Ai + SIMG;
+    const bool has_next = kt + 1 < nk;
+    if (has_next) {
+      sa.load_k(A, g.lda, m0, m_hi, k_lo + (kt + 1) * SK, k_hi);
+      sbs.load_k(B, g.ldb, n0, g.N, k_lo + (kt + 1) * SK, k_hi);
+    }
+#pragma unroll
+    for (int ks = 0; ks < SK / 16; ++ks) {
+      const bf16x8 af = AKC ? row_frag<128>(Ai, wm * 32, ks * 16, lane) : tr_frag_nat<128>(Ai, ks * 16, wm * 32, lane);
+      const bf16x8 bf = BKC ? row_frag<128>(Bi, wn * 32, ks * 16, lane) : tr_frag_nat<128>(Bi, ks * 16, wn * 32, lane);
+      acc = mfma32(bf, af, acc);
+    }
+    if (has_next) {
+      unsigned char* nxt = smem + ((kt + 1) & 1) * 2 * SIMG;
+      sa.store(nxt);
+      sbs.store(nxt + SIMG);
+    }
+    __syncthreads();
+  }
+
+  // ---- epilogue (gemms_kernel's layout): lane row m, columns n = 8 g4 + 4 h + e4
+  const int h = lane >> 5;
+  const int m = m0 + wm * 32 + (lane & 31);
+  const bool mok = m < m_hi;
+  const int64_t roff = static_cast<int64_t>(mok ? m : m0) * g.ldc + (FORM == gTN ? e * g.sC : 0);
+  const bf16* bias = g.bias ? g.bias + e * g.sBias : nullptr;
+#pragma unroll
+  for (int g4 = 0; g4 < 4; ++g4) {
+    const int n = n0 + wn * 32 + 8 * g4 + 4 * h;
+    const bool ok = mok && n < g.N;  // N % 8 == 0: a 4-group is all in or all out
+    float v[4];
+#pragma unroll
+    for (int e4 = 0; e4 < 4; ++e4) v[e4] = acc[4 * g4 + e4];
+    if (EPI == sBiasAct) {
+      if (bias && n < g.N) {
+        const bf16x4 bb = *reinterpret_cast<const bf16x4*>(bias + n);
+#pragma unroll
+        for (int e4 = 0; e4 < 4; ++e4) v[e4] += bf2f(bb[e4]);
+      }
+      if (g.pre && ok) {
+        bf16x4 pv;
+#pragma unroll
+        for (int e4 = 0; e4 < 4; ++e4) pv[e4] = f2bf(v[e4]);
+        *reinterpret_cast<bf16x4*>(g.pre + roff + n) = pv;
+      }
+#pragma unroll
+      for (int e4 = 0; e4 < 4; ++e4) v[e4] = s_act<ACT>(v[e4]);
+    }
+    if (EPI == sDact) {
+      bf16x4 xa{};
+      if (ok) xa = *reinterpret_cast<const bf16x4*>(g.aux + roff + n);
+#pragma unroll
+      for (int e4 = 0; e4 < 4; ++e4) v[e4] *= s_act_grad<ACT>(bf2f(xa[e4]));
+    }
+    if (!ok) continue;
+    if (g.out_f32) {
+      float* C = static_cast<float*>(g.C) + roff + n;
+      f32x4 o;
+      if (EPI == sPlain && g.beta != 0.f) o = *reinterpret_cast<const f32x4*>(C);
+#pragma unroll
+      for (int e4 = 0; e4 < 4; ++e4) o[e4] = v[e4] + ((EPI == sPlain && g.beta != 0.f) ? g.beta * o[e4] : 0.f);
+      *reinterpret_cast<f32x4*>(C) = o;
+    } else {
+      bf16* C = static_cast<bf16*>(g.C) + roff + n;
+      if (EPI == sPlain && g.beta != 0.f) {
+        const bf16x4 old = *reinterpret_cast<const bf16x4*>(C);
+#pragma unroll
+        for (int e4 = 0; e4 < 4; ++e4) v[e4] += g.beta * bf2f(old[e4]);
+      }
+      bf16x4 o;
+#pragma unroll
+      for (int e4 = 0; e4 < 4; ++e4) o[e4] = f2bf(v[e4]);
+      *reinterpret_cast<bf16x4*>(C) = o;
+    }
+  }
+}
+
 }  // namespace
+
+void grouped_gemm_bf16(const GroupedGemmParams& p, hipStream_t st) {
+  if (p.El <= 0 || p.N <= 0 || p.K <= 0 || p.T <= 0) return;
+  if (p.form < 0 || p.form > 2) throw std::invalid_argument("grouped_gemm: form is 0 (NN), 1 (NT) or 2 (TN)");
+  if (p.N % 8 || p.K % 8 || p.lda % 8 || p.ldb % 8 || p.ldc % 8 || p.sB % 8 || p.sC % 4 || p.sBias % 4)
+    throw std::invalid_argument("grouped_gemm: N, K, leading dimensions and group strides must be multiples of 8");
+  if ((reinterpret_cast<uintptr_t>(p.A) | reinterpret_cast<uintptr_t>(p.B) | reinterpret_cast<uintptr_t>(p.C) |
+       reinterpret_cast<uintptr_t>(p.bias) | reinterpret_cast<uintptr_t>(p.pre) | reinterpret_cast<uintptr_t>(p.aux)) & 15)
+    throw std::invalid_argument("grouped_gemm: operands must be 16-byte aligned");
+  if (!p.offsets || (p.form != gTN && (!p.tile_group || !p.tile_row0 || !p.n_tiles)))
+    throw std::invalid_argument("grouped_gemm: missing offsets / tile map");
+  const int epi = p.act_bwd ? sDact : (p.bias || p.pre || p.act) ? sBiasAct : sPlain;
+  if (p.form == gTN && p.M % 8) throw std::invalid_argument("grouped_gemm: M must be a multiple of 8");
+  if (p.form == gTN && epi != sPlain) throw std::invalid_argument("grouped_gemm: the weight-gradient form is plain");
+  if (epi != sPlain && (p.beta != 0.f || p.out_f32))
+    throw std::invalid_argument("grouped_gemm: the fused epilogues write bf16 without beta");
+  if (epi == sDact && (!p.aux || p.bias || p.pre))
+    throw std::invalid_argument("grouped_gemm: the activation-gradient epilogue needs aux, no bias / pre");
+  if (p.beta != 0.f && p.beta != 1.f) throw std::invalid_argument("grouped_gemm: beta is 0 or 1");
+  if (p.act < 0 || p.act > 4) throw std::invalid_argument("grouped_gemm: unsupported activation");
+  GemmGArgs g{static_cast<const bf16*>(p.A), static_cast<const bf16*>(p.B), p.C, static_cast<const bf16*>(p.bias),
+              static_cast<bf16*>(p.pre), static_cast<const bf16*>(p.aux), p.offsets, p.tile_group, p.tile_row0,
+              p.n_tiles, p.T, p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.sB, p.sC, p.sBias, p.beta, p.out_f32};
+  const int gn = (p.N + SN - 1) / SN;
+  dim3 grid, block(SNT);
+  if (p.form == gTN) {
+    if (p.M <= 0) return;
+    grid = dim3((p.M + SM - 1) / SM, gn, p.El);
+    if (grid.y > 65535 || grid.z > 65535) throw std::invalid_argument("grouped_gemm: grid too large");
+  } else {
+    grid = dim3(static_cast<unsigned>(p.T) * gn);
+  }
+  auto by_act = [&](auto f, auto ep) {
+    constexpr int FORM = decltype(f)::value, EPI = decltype(ep)::value;
+    switch (EPI == sPlain ? 0 : p.act) {
+      case 1: hipLaunchKernelGGL((gemmg_kernel<FORM, EPI, 1>), grid, block, 0, st, g); break;
+      case 2: hipLaunchKernelGGL((gemmg_kernel<FORM, EPI, 2>), grid, block, 0, st, g); break;
+      case 3: hipLaunchKernelGGL((gemmg_kernel<FORM, EPI, 3>), grid, block, 0, st, g); break;
+      case 4: hipLaunchKernelGGL((gemmg_kernel<FORM, EPI, 4>), grid, block, 0, st, g); break;
+      default: hipLaunchKernelGGL((gemmg_kernel<FORM, EPI, 0>), grid, block, 0, st, g); break;
+    }
+  };
+  using IC0 = std::integral_constant<int, 0>;
+  if (p.form == gTN) by_act(std::integral_constant<int, gTN>{}, std::integral_constant<int, sPlain>{});
+  else if (p.form == gNN) {
+    if (epi == sBiasAct) by_act(std::integral_constant<int, gNN>{}, std::integral_constant<int, sBiasAct>{});
+    else if (epi == sDact) by_act(std::integral_constant<int, gNN>{}, std::integral_constant<int, sDact>{});
+    else by_act(IC0{}, std::integral_constant<int, sPlain>{});
+  } else {
+    if (epi == sBiasAct) by_act(std::integral_constant<int, gNT>{}, std::integral_constant<int, sBiasAct>{});
+    else if (epi == sDact) by_act(std::integral_constant<int, gNT>{}, std::integral_constant<int, sDact>{});
+    else by_act(std::integral_constant<int, gNT>{}, std::integral_constant<int, sPlain>{});
+  }
+  FFK_LAUNCH_CHECK("grouped_gemm");
+}
 
 bool gemms_supported(const GemmPParams& p) {
   return p.K % SK == 0 && p.N % 8 == 0 && p.M % 8 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0;

@@ -164,6 +164,53 @@ void gemms_launch_batched(const GemmPParams& p, int splits, int batch, int64_t s
 void bmm_bf16(const void* A, const void* B, void* C, int batch, int M, int N, int K, int lda, int ldb, int ldc,
               int64_t sA, int64_t sB, int64_t sC, bool trans_a, bool trans_b, float alpha, float beta, int out_f32,
               hipStream_t st);
+// grouped (ragged) products on the 64x64-tile kernel: group e owns the rows
+// [offsets[e], offsets[e+1]) of A / C and the weight B + e * sB.
+//   form 0 (NN): C[rows_e] = act(A[rows_e] B[e] + bias[e])   B[e] = [K, N]
+//   form 1 (NT): C[rows_e] = A[rows_e] B[e]^T (* act'(aux))  B[e] = [N, K]
+//   form 2 (TN): C[e] = beta C[e] + A[rows_e]^T B[rows_e]    C[e] = [M, N], K unused
+// Forms 0 / 1 run over moe_route's row-tile map (T = its static size); every
+// bound is read on the device.  N, K (M for form 2) and the leading dimensions
+// are multiples of 8.
+struct GroupedGemmParams {
+  const void* A = nullptr;
+  const void* B = nullptr;
+  void* C = nullptr;
+  const void* bias = nullptr;   // [El, N] bf16 (stride sBias)
+  void* pre = nullptr;          // pre-activation out, bf16 (ldc)
+  const void* aux = nullptr;    // pre-activation in for act_bwd, bf16 (ldc)
+  const int* offsets = nullptr;     // [El + 1]
+  const int* tile_group = nullptr;  // [T]
+  const int* tile_row0 = nullptr;   // [T]
+  const int* n_tiles = nullptr;     // [1]
+  int form = 0, El = 0, T = 0, M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;
+  int64_t sB = 0, sC = 0, sBias = 0;
+  int act = 0;
+  bool act_bwd = false;
+  float beta = 0.f;
+  int out_f32 = 0;
+};
+void grouped_gemm_bf16(const GroupedGemmParams& p, hipStream_t st);
+
+// ---- moe.hip: device-side routing of the EXPERTS operator (no host sync)
+// ids [P] int32 (P = tokens * k pairs); local experts e0 .. e0 + El - 1, El <= 256.
+// offsets [El + 1], perm [P] (sorted position -> pair, stable; tail = 0),
+// pos [P] (pair -> sorted position or -1), tile_group / tile_row0 [T] with
+// T = ceil(P / 64) + El (tail: -1 / n), n_tiles [1].  ws: moe_route_ws(P, El) ints.
+int64_t moe_route_ws(int64_t P, int El);
+void moe_route(const int* ids, int64_t P, int e0, int El, int* offsets, int* perm, int* pos, int* tile_group,
+               int* tile_row0, int* n_tiles, int T, int* ws, hipStream_t st);
+// xs[p] = x[perm[p] / k] (* scale[perm[p]]) for p < n = *n_ptr, zeros beyond; bf16, D % 8 == 0
+void moe_gather_rows(const void* x, const int* perm, const void* scale, const int* n_ptr, void* xs, int64_t P,
+                     int D, int k, hipStream_t st);
+// out[b] = sum_j gate[b, j] y[pos[b, j]] over pos >= 0 (gate null: plain sum); bf16, O % 8 == 0
+void moe_combine(const void* y, const int* pos, const void* gate, void* out, int64_t B, int k, int O,
+                 hipStream_t st);
+// dgate[b, j] = <dout[b], y[pos[b, j]]> (0 where pos < 0); fp32 out
+void moe_dgate(const void* dout, const void* y, const int* pos, float* dgate, int64_t B, int k, int O,
+               hipStream_t st);
+// out[e] = column sums of x[offsets[e] : offsets[e+1]] (fp32, fixed order); N % 8 == 0
+void moe_segment_colsum(const void* x, const int* offsets, float* out, int El, int N, hipStream_t st);
 
 // ---- tensorops.hip: general tensor operators (N-d, <= 6 dims)
 struct NdShape {

@@ -15,7 +15,7 @@ import collections
 import importlib
 import math
 import os
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import torch
 
@@ -650,6 +650,376 @@ def bmm(a, b, trans_a=False, trans_b=False, out=None, beta=0.0):
               a.shape[-2] * a.shape[-1], b.shape[-2] * b.shape[-1], M * N, bool(trans_a), bool(trans_b), 1.0,
               float(beta), int(out.dtype == torch.float32), _stream())
     STATS["bmm"] += 1
+    return out
+
+
+# ---------------------------------------------------------------------------
+# Mixture-of-experts routing and grouped (ragged) GEMMs (csrc/kernels/moe.hip,
+# the grouped form of gemms.hip).  Everything is sized by the static pair
+# count P = tokens * k; the live sizes stay on the device, so the launches can
+# be captured into a hipGraph.  Each kernel has a pure-torch reference that is
+# also the CPU path.
+MOE_TILE = 64
+MOE_MAX_LOCAL_EXPERTS = 256
+
+
+class MoeRouting(NamedTuple):
+    """offsets [El+1]: exclusive prefix of the pairs per local expert
+    (offsets[El] = n local pairs); perm [P]: sorted position -> pair index,
+    expert-major and stable, positions >= n hold 0; pos [B, k]: pair -> sorted
+    position or -1; tile_group / tile_row0 [T], T = ceil(P / 64) + El: expert
+    and first row of every 64-row tile (-1 / n beyond n_tiles [1])."""
+    offsets: torch.Tensor
+    perm: torch.Tensor
+    pos: torch.Tensor
+    tile_group: torch.Tensor
+    tile_row0: torch.Tensor
+    n_tiles: torch.Tensor
+    k: int
+
+    @property
+    def num_local(self) -> int:
+        return self.offsets.numel() - 1
+
+    @property
+    def pairs(self) -> int:
+        return self.perm.numel()
+
+
+def moe_num_tiles(P: int, El: int) -> int:
+    return (P + MOE_TILE - 1) // MOE_TILE + El
+
+
+def moe_route_reference(ids, e0: int, El: int) -> MoeRouting:
+    B, k = ids.shape
+    P, dev = B * k, ids.device
+    eg = ids.reshape(-1).long()
+    sel = ((eg >= e0) & (eg < e0 + El)).nonzero().squeeze(1)
+    le = eg[sel] - e0
+    sel = sel[torch.argsort(le, stable=True)]
+    n = sel.numel()
+    counts = torch.bincount(le, minlength=El)
+    offsets = torch.zeros(El + 1, dtype=torch.int64, device=dev)
+    offsets[1:] = torch.cumsum(counts, 0)
+    perm = torch.zeros(P, dtype=torch.int32, device=dev)
+    perm[:n] = sel.to(torch.int32)
+    pos = torch.full((P,), -1, dtype=torch.int32, device=dev)
+    pos[sel] = torch.arange(n, dtype=torch.int32, device=dev)
+    T = moe_num_tiles(P, El)
+    tg, tr = [], []
+    off = offsets.tolist()
+    for e in range(El):
+        for r in range(off[e], off[e + 1], MOE_TILE):
+            tg.append(e)
+            tr.append(r)
+    nt = len(tg)
+    tg += [-1] * (T - nt)
+    tr += [n] * (T - nt)
+    i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=dev)  # noqa: E731
+    return MoeRouting(offsets.to(torch.int32), perm, pos.view(B, k), i32(tg), i32(tr), i32([nt]), k)
+
+
+def moe_route(ids, e0: int, El: int) -> MoeRouting:
+    """Route the (token, slot) pairs of ``ids`` [B, k] (int32) to the local
+    experts e0 .. e0+El-1 on the device (three launches, no host sync,
+    deterministic)."""
+    if ids.dim() != 2 or ids.dtype != torch.int32:
+        raise ValueError("moe_route: ids must be [B, k] int32")
+    if not 1 <= El <= MOE_MAX_LOCAL_EXPERTS:
+        raise ValueError(f"moe_route: 1 <= local experts <= {MOE_MAX_LOCAL_EXPERTS}")
+    if not ids.is_cuda:
+        return moe_route_reference(ids, e0, El)
+    _check(ids, "ids", torch.int32, aligned=False)
+    B, k = ids.shape
+    P = B * k
+    if P < 1:
+        raise ValueError("moe_route: no pairs")
+    T = moe_num_tiles(P, El)
+    nws = int(ext().moe_route_ws(P, El))
+    # one allocation: offsets | n_tiles | perm | pos | tile_group | tile_row0 | workspace
+    buf = torch.empty(El + 2 + 2 * P + 2 * T + nws, dtype=torch.int32, device=ids.device)
+    offsets, n_tiles, perm, pos, tg, tr, ws = torch.split(buf, [El + 1, 1, P, P, T, T, nws])
+    ext().moe_route(_p(ids), P, int(e0), int(El), _p(offsets), _p(perm), _p(pos), _p(tg), _p(tr), _p(n_tiles), T,
+                    _p(ws), _stream())
+    STATS["moe_route"] += 1
+    return MoeRouting(offsets, perm, pos.view(B, k), tg, tr, n_tiles, k)
+
+
+def moe_gather_rows_reference(x, route: MoeRouting, scale=None):
+    n = int(route.offsets[-1])
+    xs = torch.zeros(route.pairs, x.shape[1], dtype=x.dtype, device=x.device)
+    pr = route.perm[:n].long()
+    rows = x[pr // route.k].float()
+    if scale is not None:
+        rows = rows * scale.reshape(-1)[pr].float().unsqueeze(1)
+    xs[:n] = rows.to(x.dtype)
+    return xs
+
+
+def moe_gather_rows(x, route: MoeRouting, scale=None):
+    """xs[p] = x[perm[p] // k] (* scale[perm[p]]) for the n local pairs in
+    sorted order, zeros in the rows beyond; x [B, D], scale [B, k]."""
+    if x.dim() != 2 or x.shape[0] * route.k != route.pairs:
+        raise ValueError("moe_gather_rows: x must be [B, D] with B * k routed pairs")
+    if scale is not None and scale.numel() != route.pairs:
+        raise ValueError("moe_gather_rows: scale must hold one value per pair")
+    if not x.is_cuda:
+        return moe_gather_rows_reference(x, route, scale)
+    _check(x, "x", torch.bfloat16)
+    if scale is not None:
+        _check(scale, "scale", torch.bfloat16, aligned=False)
+    D = x.shape[1]
+    if D % 8:
+        raise ValueError("moe_gather_rows: D must be a multiple of 8")
+    xs = torch.empty(route.pairs, D, dtype=x.dtype, device=x.device)
+    ext().moe_gather_rows(_p(x), _p(route.perm), _p(scale), route.offsets.data_ptr() + 4 * route.num_local, _p(xs),
+                          route.pairs, D, route.k, _stream())
+    STATS["moe_gather_rows"] += 1
+    return xs
+
+
+def moe_combine_reference(y, route: MoeRouting, gate=None):
+    pos = route.pos.long()
+    rows = y.float()[pos.clamp(min=0)]                       # [B, k, O]
+    w = (pos >= 0).float() if gate is None else gate.float() * (pos >= 0).float()
+    return (rows * w.unsqueeze(-1)).sum(1).to(y.dtype)
+
+
+def moe_combine(y, route: MoeRouting, gate=None):
+    """out[b] = sum_j gate[b, j] * y[pos[b, j]] over the local pairs of token
+    b (``gate`` None: plain sum); a per-token gather, no atomics."""
+    if y.dim() != 2 or y.shape[0] != route.pairs:
+        raise ValueError("moe_combine: y must be [P, O]")
+    if gate is not None and tuple(gate.shape) != tuple(route.pos.shape):
+        raise ValueError("moe_combine: gate must be [B, k]")
+    if not y.is_cuda:
+        return moe_combine_reference(y, route, gate)
+    _check(y, "y", torch.bfloat16)
+    if gate is not None:
+        _check(gate, "gate", torch.bfloat16, aligned=False)
+    B, k = route.pos.shape
+    O = y.shape[1]
+    if O % 8:
+        raise ValueError("moe_combine: O must be a multiple of 8")
+    out = torch.empty(B, O, dtype=y.dtype, device=y.device)
+    ext().moe_combine(_p(y), _p(route.pos), _p(gate), _p(out), B, k, O, _stream())
+    STATS["moe_combine"] += 1
+    return out
+
+
+def moe_dgate_reference(dout, y, route: MoeRouting):
+    pos = route.pos.long()
+    rows = y.float()[pos.clamp(min=0)]
+    return (rows * dout.float().unsqueeze(1)).sum(-1) * (pos >= 0).float()
+
+
+def moe_dgate(dout, y, route: MoeRouting):
+    """dgate[b, j] = <dout[b], y[pos[b, j]]> (0 for a pair that is not local);
+    fp32 [B, k]."""
+    B, k = route.pos.shape
+    if dout.dim() != 2 or dout.shape[0] != B or tuple(y.shape) != (route.pairs, dout.shape[1]):
+        raise ValueError("moe_dgate: dout [B, O], y [P, O]")
+    if not dout.is_cuda:
+        return moe_dgate_reference(dout, y, route)
+    _check(dout, "dout", torch.bfloat16)
+    _check(y, "y", torch.bfloat16)
+    O = y.shape[1]
+    if O % 8:
+        raise ValueError("moe_dgate: O must be a multiple of 8")
+    dg = torch.empty(B, k, dtype=torch.float32, device=y.device)
+    ext().moe_dgate(_p(dout), _p(y), _p(route.pos), _p(dg), B, k, O, _stream())
+    STATS["moe_dgate"] += 1
+    return dg
+
+
+def moe_segment_colsum_reference(x, route: MoeRouting):
+    off = route.offsets.tolist()
+    return torch.stack([x[off[e]:off[e + 1]].float().sum(0) for e in range(route.num_local)])
+
+
+def moe_segment_colsum(x, route: MoeRouting, out=None):
+    """out[e] = column sums of expert e's rows of x [P, N] (fp32 [El, N], fixed
+    summation order: the bias gradients)."""
+    if x.dim() != 2 or x.shape[0] != route.pairs:
+        raise ValueError("moe_segment_colsum: x must be [P, N]")
+    if not x.is_cuda:
+        r = moe_segment_colsum_reference(x, route)
+        return r if out is None else out.copy_(r)
+    _check(x, "x", torch.bfloat16)
+    N = x.shape[1]
+    if N % 8:
+        raise ValueError("moe_segment_colsum: N must be a multiple of 8")
+    if out is None:
+        out = torch.empty(route.num_local, N, dtype=torch.float32, device=x.device)
+    _check(out, "out", torch.float32, route.num_local * N, aligned=False)
+    ext().moe_segment_colsum(_p(x), _p(route.offsets), _p(out), route.num_local, N, _stream())
+    STATS["moe_segment_colsum"] += 1
+    return out
+
+
+_GROUPED_FORMS = {"nn": 0, "nt": 1, "tn": 2}
+
+
+def _grouped_dims(a, b, form: str):
+    """(El or None, rows of C per group or None, N, K or None)."""
+    if form not in _GROUPED_FORMS:
+        raise ValueError(f"grouped_gemm: form is one of {sorted(_GROUPED_FORMS)}")
+    if form == "tn":
+        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[0]:
+            raise ValueError("grouped_gemm tn: a [P, M], b [P, N]")
+        return None, int(a.shape[1]), int(b.shape[1]), None
+    if a.dim() != 2 or b.dim() != 3:
+        raise ValueError("grouped_gemm: a [P, K], b [El, ., .]")
+    Kd, N = (int(b.shape[1]), int(b.shape[2])) if form == "nn" else (int(b.shape[2]), int(b.shape[1]))
+    if Kd != a.shape[1]:
+        raise ValueError(f"grouped_gemm: inner dims differ ({a.shape[1]} vs {Kd})")
+    return int(b.shape[0]), None, N, Kd
+
+
+def grouped_gemm_supported(a, b, form: str = "nn") -> bool:
+    """bf16 GPU operands, contiguous, 16-byte aligned, every feature dimension
+    (and so every leading dimension) a multiple of 8; the ragged row bounds
+    are arbitrary."""
+    if not a.is_cuda or not b.is_cuda or not available() or not hasattr(ext(), "grouped_gemm"):
+        return False
+    return grouped_gemm_layout_ok(a, b, form)
+
+
+def grouped_gemm_layout_ok(a, b, form: str = "nn") -> bool:
+    """The device-independent part of ``grouped_gemm_supported``: dtype,
+    contiguity, alignment and the multiples of 8."""
+    if form not in _GROUPED_FORMS:
+        return False
+    for t in (a, b):
+        if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.data_ptr() % 16:
+            return False
+    try:
+        El, M, N, Kd = _grouped_dims(a, b, form)
+    except ValueError:
+        return False
+    if El is not None and not 1 <= El <= MOE_MAX_LOCAL_EXPERTS:
+        return False
+    return all(d % 8 == 0 and d > 0 for d in (M, N, Kd) if d is not None)
+
+
+def _act_grad_reference(pre, act: str):
+    p = pre.detach().clone().requires_grad_(True)
+    fn = {"none": lambda t: t, "identity": lambda t: t, "relu": torch.relu, "sigmoid": torch.sigmoid,
+          "tanh": torch.tanh, "gelu": lambda t: torch.nn.functional.gelu(t, approximate="tanh")}[act]
+    with torch.enable_grad():
+        return torch.autograd.grad(fn(p).sum(), p)[0]
+
+
+def grouped_gemm_reference(a, b, route: MoeRouting, form: str = "nn", bias=None, act: str = "none", pre=None,
+                           aux=None, dbias=None, out=None, beta: float = 0.0, out_dtype=None):
+    """Per-group torch products with the kernel's rounding points (fp32
+    accumulation, bf16 pre-activation); rows beyond the local pairs of a given
+    ``out`` stay as they are."""
+    off = route.offsets.tolist()
+    El, M, N, _ = _grouped_dims(a, b, form)
+    fwd = {"none": lambda t: t, "identity": lambda t: t, "relu": torch.relu, "sigmoid": torch.sigmoid,
+           "tanh": torch.tanh, "gelu": lambda t: torch.nn.functional.gelu(t, approximate="tanh")}[act]
+    if form == "tn":
+        El = route.num_local
+        if out is None:
+            out = torch.zeros(El, M, N, dtype=out_dtype or torch.float32, device=a.device)
+            beta = 0.0
+        for e in range(El):
+            lo, hi = off[e], off[e + 1]
+            if hi == lo and beta:
+                continue
+            r = a[lo:hi].float().t() @ b[lo:hi].float()
+            out[e] = (r + out[e].float() if beta else r).to(out.dtype)
+        return out
+    if out is None:
+        out = torch.zeros(a.shape[0], N, dtype=a.dtype, device=a.device)
+    for e in range(El):
+        lo, hi = off[e], off[e + 1]
+        if hi == lo:
+            continue
+        w = b[e].float() if form == "nn" else b[e].float().t()
+        r = a[lo:hi].float() @ w
+        if bias is not None:
+            r = r + bias[e].float()
+        if pre is not None:
+            pre[lo:hi] = r.to(pre.dtype)
+        if aux is not None:
+            r = r * _act_grad_reference(aux[lo:hi].float(), act)
+        else:
+            r = fwd(r)
+        out[lo:hi] = r.to(out.dtype)
+    if dbias is not None:
+        dbias.copy_(moe_segment_colsum_reference(out, route))
+    return out
+
+
+def grouped_gemm(a, b, route: MoeRouting, form: str = "nn", bias=None, act: str = "none", pre=None, aux=None,
+                 dbias=None, out=None, beta: float = 0.0, out_dtype=None):
+    """Ragged products over the expert row blocks of ``route`` in one launch
+    (64x64-tile MFMA kernel, bounds read on the device):
+
+      nn: out[rows_e] = act(a[rows_e] @ b[e] + bias[e])   b [El, K, N]; ``pre`` [P, N] receives the
+                                                          pre-activation
+      nt: out[rows_e] = a[rows_e] @ b[e]^T                b [El, N, K]; with ``aux`` [P, N] the result
+                                                          is multiplied by act'(aux)
+      tn: out[e] = beta * out[e] + a[rows_e]^T @ b[rows_e]  a [P, M], b [P, N]; out [El, M, N] fp32 / bf16,
+                                                          beta 0 or 1
+
+    ``dbias`` (fp32 [El, N], overwritten) receives the per-expert column sums of
+    the result: a separate fixed-order kernel, not the epilogue's atomics, so
+    the sums are reproducible.  Rows of ``out`` beyond the local pairs are
+    never written."""
+    El, M, N, Kd = _grouped_dims(a, b, form)
+    if not a.is_cuda:
+        return grouped_gemm_reference(a, b, route, form, bias, act, pre, aux, dbias, out, beta, out_dtype)
+    if not grouped_gemm_supported(a, b, form):
+        raise ValueError("grouped_gemm: unsupported operands")
+    if a.shape[0] != route.pairs:
+        raise ValueError("grouped_gemm: a must have one row per routed pair")
+    code = ACT_CODES[act]
+    if code > 4:
+        raise ValueError(f"grouped_gemm: unsupported activation {act}")
+    if beta not in (0.0, 1.0):
+        raise ValueError("grouped_gemm: beta is 0 or 1")
+    P = route.pairs
+    T = route.tile_group.numel()
+    if form == "tn":
+        El = route.num_local
+        if bias is not None or pre is not None or aux is not None or dbias is not None or code:
+            raise ValueError("grouped_gemm tn: plain epilogue only")
+        if out is None:
+            out = torch.empty(El, M, N, dtype=out_dtype or torch.float32, device=a.device)
+            beta = 0.0
+        if tuple(out.shape) != (El, M, N) or out.dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("grouped_gemm tn: out must be [El, M, N] fp32 or bf16")
+        _check(out, "out")
+        ext().grouped_gemm(2, _p(a), _p(b), _p(out), 0, 0, 0, _p(route.offsets), 0, 0, 0, El, T, M, N, 8,
+                           M, N, N, 0, M * N, 0, 0, False, float(beta), int(out.dtype == torch.float32), _stream())
+        STATS["grouped_gemm"] += 1
+        return out
+    if El != route.num_local:
+        raise ValueError("grouped_gemm: b must hold one matrix per local expert")
+    if beta:
+        raise ValueError("grouped_gemm: the row-block forms overwrite their output")
+    if out is None:
+        out = torch.empty(P, N, dtype=torch.bfloat16, device=a.device)
+    if tuple(out.shape) != (P, N):
+        raise ValueError("grouped_gemm: out must be [P, N]")
+    _check(out, "out", torch.bfloat16)
+    if bias is not None:
+        _check(bias, "bias", torch.bfloat16, El * N)
+    if pre is not None:
+        _check(pre, "pre", torch.bfloat16, P * N)
+    if aux is not None:
+        _check(aux, "aux", torch.bfloat16, P * N)
+        if bias is not None or pre is not None:
+            raise ValueError("grouped_gemm: the activation-gradient epilogue takes no bias / pre")
+    ext().grouped_gemm(_GROUPED_FORMS[form], _p(a), _p(b), _p(out), _p(bias), _p(pre), _p(aux), _p(route.offsets),
+                       _p(route.tile_group), _p(route.tile_row0), _p(route.n_tiles), El, T, 0, N, Kd,
+                       Kd, b.shape[2], N, b.shape[1] * b.shape[2], 0, N, code, aux is not None, 0.0, 0, _stream())
+    STATS["grouped_gemm"] += 1
+    if dbias is not None:
+        moe_segment_colsum(out, route, out=dbias)
     return out
 
 
