@@ -114,6 +114,31 @@ __device__ __forceinline__ float gelu_tanh_grad(float x) {
   const float w = x * __builtin_fmaf(k0x2 * k1x3, x2, k0x2);
   return __builtin_fmaf(w, s - s * s, s);
 }
+// activation code (elementwise.hip numbering) fixed at compile time: a run-time
+// switch in a GEMM epilogue keeps hipcc from unrolling it, which then indexes
+// the AGPR accumulators dynamically through scratch
+template <int ACT>
+__device__ __forceinline__ float act_ct(float x) {
+  if (ACT == 1) return x > 0.f ? x : 0.f;
+  if (ACT == 2) return 1.f / (1.f + __expf(-x));
+  if (ACT == 3) return fast_tanh(x);
+  if (ACT == 4) return gelu_tanh(x);
+  return x;
+}
+template <int ACT>
+__device__ __forceinline__ float act_grad_ct(float x) {
+  if (ACT == 1) return x > 0.f ? 1.f : 0.f;
+  if (ACT == 2) {
+    const float s = 1.f / (1.f + __expf(-x));
+    return s * (1.f - s);
+  }
+  if (ACT == 3) {
+    const float t = fast_tanh(x);
+    return 1.f - t * t;
+  }
+  if (ACT == 4) return gelu_tanh_grad(x);
+  return 1.f;
+}
 
 // Counter-based RNG (splitmix64 finaliser) for dropout: deterministic in
 // (seed, offset, element index), so forward and backward regenerate the same

@@ -68,32 +68,6 @@ struct GemmTArgs {
   int dbg;   // ablation bits (timing experiments, tools/gemm_ablate.py)
 };
 
-// activation code (elementwise.hip numbering) fixed at compile time: a run-time
-// switch here keeps hipcc from unrolling the epilogue, which then indexes the
-// AGPR accumulators dynamically through scratch
-template <int ACT>
-__device__ __forceinline__ float t_act(float x) {
-  if (ACT == 1) return x > 0.f ? x : 0.f;
-  if (ACT == 2) return 1.f / (1.f + __expf(-x));
-  if (ACT == 3) return fast_tanh(x);
-  if (ACT == 4) return gelu_tanh(x);
-  return x;
-}
-template <int ACT>
-__device__ __forceinline__ float t_act_grad(float x) {
-  if (ACT == 1) return x > 0.f ? 1.f : 0.f;
-  if (ACT == 2) {
-    const float s = 1.f / (1.f + __expf(-x));
-    return s * (1.f - s);
-  }
-  if (ACT == 3) {
-    const float t = fast_tanh(x);
-    return 1.f - t * t;
-  }
-  if (ACT == 4) return gelu_tanh_grad(x);
-  return 1.f;
-}
-
 typedef float f32x2t __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2t __attribute__((ext_vector_type(2)));
 
@@ -110,7 +84,7 @@ template <int ACT>
 __device__ __forceinline__ f32x2t t_act2(f32x2t x) {
   if (ACT == 1) return f32x2t{x.x > 0.f ? x.x : 0.f, x.y > 0.f ? x.y : 0.f};
   if (ACT == 4) return x * gelu_sig2(x, x * x);
-  return f32x2t{t_act<ACT>(x.x), t_act<ACT>(x.y)};
+  return f32x2t{act_ct<ACT>(x.x), act_ct<ACT>(x.y)};
 }
 // g * act'(x)
 template <int ACT>
@@ -123,7 +97,7 @@ __device__ __forceinline__ f32x2t t_dact2(f32x2t g, f32x2t x) {
     const f32x2t w = x * __builtin_elementwise_fma(x2, f32x2t{k0x2 * k1x3, k0x2 * k1x3}, f32x2t{k0x2, k0x2});
     return g * __builtin_elementwise_fma(w, sg - sg * sg, sg);
   }
-  return f32x2t{g.x * t_act_grad<ACT>(x.x), g.y * t_act_grad<ACT>(x.y)};
+  return f32x2t{g.x * act_grad_ct<ACT>(x.x), g.y * act_grad_ct<ACT>(x.y)};
 }
 // bf16 pair (one dword) -> float2: low half << 16, high half masked
 __device__ __forceinline__ f32x2t unpack2(unsigned u) {

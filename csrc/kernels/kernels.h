@@ -154,7 +154,9 @@ void gemmn_launch(const GemmPParams& p, hipStream_t st);
 // eight-wave ping-pong A B^T GEMM, variant 11 (gemmpp.hip)
 bool gemmpp_supported(const GemmPParams& p);
 void gemmpp_launch(const GemmPParams& p, hipStream_t st);
-// small-tile (64 x 64) MLP GEMM, variant 8 (gemms.hip)
+// small-tile (64 x 64) MLP GEMM, variant 8 (gemms.hip).  The dense, batched and
+// grouped entry points below run one kernel body (K loop + epilogue) and differ
+// only in where a workgroup's tile lies, so equal operands give equal bits.
 bool gemms_supported(const GemmPParams& p);
 void gemms_launch(const GemmPParams& p, int splits, hipStream_t st);
 void gemms_launch_batched(const GemmPParams& p, int splits, int batch, int64_t sA, int64_t sB, int64_t sC,

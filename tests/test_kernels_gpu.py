@@ -497,3 +497,30 @@ def test_bmm(ta, tb, Z, M, N, Kd):
     acc = torch.ones(Z, M, N, device=DEV, dtype=torch.float32)
     K.bmm(a, b, ta, tb, out=acc, beta=1.0)
     assert _rel(acc, ref + 1) < _F32
+
+
+def test_grouped_single_group_equals_dense():
+    """gemms.hip runs one tile program behind the dense (variant 8) and the
+    grouped entry points, and ops/moe.py relies on the two agreeing: a grouped
+    NN product whose single group owns all 130 rows equals the dense product
+    of the same operands bit for bit, output and pre-activation, plain and
+    with bias + GELU.  The dense launcher takes M % 8 == 0 only, so it runs on
+    136 rows of which the first 130 are the grouped operand (rows are
+    independent)."""
+    torch.manual_seed(21)
+    M, Kd, N = 130, 192, 72
+    a8 = torch.randn(136, Kd, device=DEV, dtype=torch.bfloat16)
+    a = a8[:M]
+    w = torch.randn(1, Kd, N, device=DEV, dtype=torch.bfloat16) * 0.1
+    bias = torch.randn(1, N, device=DEV, dtype=torch.bfloat16)
+    r = K.moe_route(torch.zeros(M, 1, device=DEV, dtype=torch.int32), 0, 1)
+    assert r.offsets.tolist() == [0, M]
+    dense = K.gemmp(a8, w[0], variant=8)
+    assert _rel(dense, a8.float() @ w[0].float()) < _BF
+    assert torch.equal(K.grouped_gemm(a, w, r, "nn"), dense[:M])
+    pre_g = torch.empty(M, N, device=DEV, dtype=torch.bfloat16)
+    pre_d = torch.empty(136, N, device=DEV, dtype=torch.bfloat16)
+    out_g = K.grouped_gemm(a, w, r, "nn", bias=bias, act="gelu", pre=pre_g)
+    out_d = K.gemmp(a8, w[0], bias=bias[0], act="gelu", pre=pre_d, variant=8)
+    assert torch.equal(pre_g, pre_d[:M])
+    assert torch.equal(out_g, out_d[:M])

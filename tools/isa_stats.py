@@ -26,7 +26,7 @@ def kernels(lines):
     for i, l in enumerate(lines):
         m = re.match(r"^(_Z\w+):", l)
         if m:
-            j = next(k for k in range(i, len(lines)) if lines[k].strip().startswith("s_endpgm"))
+            j = next(k for k in range(i, len(lines)) if lines[k].startswith(".Lfunc_end"))  # not the first s_endpgm
             yield m.group(1), i, j
 
 
@@ -39,7 +39,7 @@ def meta(text, name):
     for l in text[i:j].split("\n"):
         p = l.split()
         if len(p) == 2 and p[0] in (".amdhsa_next_free_vgpr", ".amdhsa_accum_offset",
-                                    ".amdhsa_private_segment_fixed_size"):
+                                    ".amdhsa_private_segment_fixed_size", ".amdhsa_group_segment_fixed_size"):
             out[p[0].split("_", 1)[1]] = int(p[1])
     return out
 
@@ -51,9 +51,12 @@ def summarise(lines, st, end):
     if not hdr:
         return {"total": len(ins(body))}
     h = hdr[-1]
-    lab = body[h].split(":")[0]
-    e = next((i for i, l in enumerate(body) if "s_cbranch" in l and l.strip().endswith(lab)), None)
-    loop = ins(body[h:e + 1]) if e else []
+    labels = {l.split(":")[0]: i for i, l in enumerate(body) if l.startswith(".LBB")}
+    # the back edge: the first branch below the header to a label at or above it
+    # (the loop's latch block may be laid out just above the header)
+    s, e = next(((labels[l.split()[-1]], i) for i, l in enumerate(body)
+                 if i > h and "branch" in l and labels.get(l.split()[-1], i) <= h), (None, None))
+    loop = ins(body[s:e + 1]) if e else []
     post = ins(body[e + 1:]) if e else []
     return {"loop": len(loop), "loop_mix": collections.Counter(loop).most_common(12), "post": len(post),
             "post_mix": collections.Counter(post).most_common(16)}
