@@ -300,7 +300,11 @@ void sparse_sgd_rows(const SparseSgdArgs& a, float* scratch, float step, hipStre
 
 void sum_squares(const float* x, int64_t n, float* out, hipStream_t st) {
   need4(n, "sum_squares");
-  int grid = grid_for(n / 4, 256, 1024);
+  // every block ends in one fp32 atomic onto the running total, each of which
+  // rounds at the total's size: at least 8 loads per thread before a buffer is
+  // split over more blocks (280k elements had gone to 274 blocks and came out
+  // 5e-7 off, in an order that changes from run to run; 35 blocks now)
+  int grid = grid_for(n / 4, 256 * 8, 1024);
   hipLaunchKernelGGL(sumsq_kernel, dim3(grid), dim3(256), 0, st, x, n / 4, out);
   FFK_LAUNCH_CHECK("sum_squares");
 }

@@ -184,6 +184,8 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(T* __restrict__ logits,
   if (!write_grad) return;
   __syncthreads();  // the label logit must be read before it is overwritten
   const float scale = valid ? grad_scale : 0.f;
+  // a row that does not count has no label column: (p - 1) * 0 would store -0
+  const long long hot = valid ? lab : -1;
   if (VEC) {
     for (int c = threadIdx.x * 8; c < V; c += 256 * 8) {
       float v[8];
@@ -202,7 +204,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(T* __restrict__ logits,
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float p = (c + k < V_valid) ? __expf(v[k] - lse) : 0.f;
-        v[k] = (p - ((c + k) == lab ? 1.f : 0.f)) * scale;
+        v[k] = (p - ((c + k) == hot ? 1.f : 0.f)) * scale;
       }
       if constexpr (sizeof(T) == 2) {
         bf16x8 o;
@@ -223,7 +225,7 @@ __global__ __launch_bounds__(256) void softmax_ce_kernel(T* __restrict__ logits,
   } else {
     for (int c = threadIdx.x; c < V; c += 256) {
       float p = (c < V_valid) ? __expf(ldf<T>(x + c) - lse) : 0.f;
-      stf<T>(x + c, (p - (c == lab ? 1.f : 0.f)) * scale);
+      stf<T>(x + c, (p - (c == hot ? 1.f : 0.f)) * scale);
     }
   }
 }

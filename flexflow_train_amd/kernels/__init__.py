@@ -248,6 +248,14 @@ def softmax_bwd(dy, y):
     return dx
 
 
+def _check_grad(g, n):
+    """A flat gradient: fp32 is read 16 bytes at a time; bf16 may start on any
+    8 bytes (a slice of a flat bf16 buffer), which the 4-wide kernels read."""
+    _check(g, "g", numel=n, aligned=False)
+    if g.data_ptr() % (8 if g.dtype == torch.bfloat16 else 16):
+        raise ValueError("g: data pointer must be 16-byte aligned (8-byte for bf16)")
+
+
 def adam_step(w, g, m, v, w_bf16, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0, decoupled=False,
               hp=None):
     """Fused Adam/AdamW over a flat buffer; g may be fp32 or bf16.  ``hp``: optional
@@ -257,7 +265,7 @@ def adam_step(w, g, m, v, w_bf16, lr, beta1, beta2, eps, weight_decay, step, gra
     n = w.numel()
     for name, t in (("w", w), ("m", m), ("v", v)):
         _check(t, name, torch.float32, n)
-    _check(g, "g", numel=n)
+    _check_grad(g, n)
     if w_bf16 is not None:
         _check(w_bf16, "w_bf16", torch.bfloat16, n)
     if n % 4:
@@ -270,7 +278,7 @@ def adam_step(w, g, m, v, w_bf16, lr, beta1, beta2, eps, weight_decay, step, gra
 def sgd_step(w, g, mom, w_bf16, lr, momentum, weight_decay, nesterov, grad_scale=1.0):
     n = w.numel()
     _check(w, "w", torch.float32, n)
-    _check(g, "g", numel=n)
+    _check_grad(g, n)
     if mom is not None:
         _check(mom, "mom", torch.float32, n)
     if w_bf16 is not None:

@@ -42,6 +42,10 @@ def _rel64(a, b):
 # intermediates (attention's P / dS operands), measured at 1.6-2.5e-3
 # (profiles/r6/g01_tol_probe.jsonl); a 1 % error in one tile phase fails
 _BF_OP = 5e-3
+# fp32 optimizer updates (w_after - w_before) against fp64: 8x the fp32 floor of
+# the same formula, as in test_rowwise_paths_gpu.py
+# (profiles/r9/rowwise_tolerances.txt: adam_update, sgd_update)
+_ADAM_UPD, _SGD_UPD = 4e-4, 3e-4
 
 
 @pytest.mark.parametrize("N", [1024, 768, 4096, 200 * 8])
@@ -124,9 +128,12 @@ def test_softmax_ce(V, Vv, ldt):
     assert g[5].abs().max().item() == 0         # ignored row: zero gradient
     if V > Vv:
         assert g[:, Vv:].abs().max().item() == 0
+    # a row is correct when its label is the FIRST index of its maximum (the
+    # kernel's rule; argmax leaves ties open): exact count
     valid = labels >= 0
-    acc = (lf0.argmax(1) == labels)[valid].float().sum().item()
-    assert abs(metrics[1].item() - acc) <= 2
+    first = torch.where(lf0 == lf0.max(1, keepdim=True).values, torch.arange(Vv, device=DEV), Vv).min(1).values
+    acc = (first == labels)[valid].sum().item()
+    assert metrics[1].item() == acc
 
 
 def test_softmax_fwd_bwd():
@@ -145,6 +152,7 @@ def test_adam_and_sgd():
     torch.manual_seed(4)
     n = 4096 * 3
     w = torch.randn(n, device=DEV)
+    w0 = w.clone()
     g = torch.randn(n, device=DEV)
     m = torch.zeros(n, device=DEV)
     v = torch.zeros(n, device=DEV)
@@ -157,9 +165,14 @@ def test_adam_and_sgd():
         K.adam_step(w, g, m, v, wb, 1e-3, 0.9, 0.999, 1e-8, 0.01 * 1e-3 / 1e-3, step, decoupled=True)
     # AdamW decoupled decay in torch multiplies by lr: w -= lr*wd*w; ours adds wd*w to the update scaled by lr
     assert _rel(w, ref_p.detach()) < 1e-5
-    assert _rel(wb, w) < 1e-2
+    # the weights are O(1) and move by lr per step: compare the movement too.
+    # torch's fp32 step is itself at most one floor (bound / 8) from exact and
+    # the kernel at most one bound, so twice the bound holds for the pair
+    assert _rel(w - w0, ref_p.detach() - w0) < 2 * _ADAM_UPD
+    assert torch.equal(wb, w.to(torch.bfloat16))   # the compute copy is the rounded master
     # SGD with momentum + nesterov + weight decay against torch.optim.SGD
     w2 = torch.randn(n, device=DEV)
+    w2_0 = w2.clone()
     mom = torch.zeros(n, device=DEV)
     p2 = torch.nn.Parameter(w2.clone())
     opt2 = torch.optim.SGD([p2], lr=0.1, momentum=0.9, nesterov=True, weight_decay=1e-4)
@@ -168,6 +181,7 @@ def test_adam_and_sgd():
         opt2.step()
         K.sgd_step(w2, g, mom, None, 0.1, 0.9, 1e-4, True)
     assert _rel(w2, p2.detach()) < 1e-5
+    assert _rel(w2 - w2_0, p2.detach() - w2_0) < 2 * _SGD_UPD
 
 
 @pytest.mark.parametrize("aggr", ["none", "sum", "avg"])
