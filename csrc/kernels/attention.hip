@@ -24,7 +24,9 @@
 //  * backward = dQ kernel (query block resident; also computes delta =
 //    rowsum(dO*O) for its queries) then dK/dV kernel (key block resident,
 //    loops over query tiles, key on the lane) -> no float atomics,
-//    deterministic, no [N, N] buffers.
+//    deterministic, no [N, N] buffers.  Non-causal D = 64 calls with at most
+//    512 keys take the one-pass kernel instead (attn_bwd_onepass_kernel): one
+//    workgroup per (batch, head), all three gradients from one S / dS.
 //
 // Tensor addressing: every tensor is [B, S, H, D] with arbitrary strides for
 // b / s / h and contiguous d, so the fused QKV projection output
@@ -144,16 +146,16 @@ __device__ __forceinline__ void bias_colsum(const f32x16 (&acc)[DT], float mul, 
     }
 }
 
-// Global [rows][D] tile -> registers (each thread `per` chunks of 16 B).
-template <int D, int ROWS>
+// Global [rows][D] tile -> registers (each of NT threads `per` chunks of 16 B).
+template <int D, int ROWS, int NT = 256>
 struct TileLoader {
   static constexpr int CHUNKS = ROWS * D / 8;
-  static constexpr int PER = CHUNKS / 256;
+  static constexpr int PER = CHUNKS / NT;
   bf16x8 reg[PER];
   __device__ __forceinline__ void load(const TensorView& t, int b, int h, int row0, int nrows) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int c = threadIdx.x + 256 * i;
+      const int c = threadIdx.x + NT * i;
       const int r = c / (D / 8), ch = c % (D / 8);
       if (row0 + r < nrows) {
         reg[i] = *reinterpret_cast<const bf16x8*>(t.p + b * t.sb + static_cast<int64_t>(row0 + r) * t.ss +
@@ -166,7 +168,7 @@ struct TileLoader {
   __device__ __forceinline__ void store(unsigned char* img) const {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
-      const int c = threadIdx.x + 256 * i;
+      const int c = threadIdx.x + NT * i;
       const int r = c / (D / 8), ch = c % (D / 8);
       *reinterpret_cast<bf16x8*>(img + lds_off<D>(r, ch)) = reg[i];
     }
@@ -962,6 +964,283 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
 }
 
 // ===========================================================================
+// One-pass backward for D = 64, non-causal, Sk <= 512, no dbias: S, P, dP and
+// dS are formed once per (query, key) tile and feed all three gradients —
+// five MFMA products and one exp2 per pair instead of the seven and two of
+// the dQ + dK/dV kernel pair, and Q / K / V / dO are fetched once.
+//
+// One workgroup (8 waves, two per SIMD) owns every key of one (batch, head)
+// and walks them in at most two resident 256-key blocks.  A wave is the
+// dK/dV kernel's wave: 32 keys on its lanes, dK^T / dV^T of those keys in
+// registers over the whole sweep of 64-query tiles.  Added to it:
+//  * dS^T crosses LDS once, as a [key][query] image of 128-byte rows (the
+//    Q / K image format), double buffered; the tile's existing barrier
+//    publishes it;
+//  * dQ^T(tile) = K^T dS^T over the block's 256 keys, from transposed reads
+//    of that image and of a K image of the block.  Four waves own the four
+//    32 x 32 pieces of an even tile's dQ, the other four those of an odd
+//    tile's, each one iteration behind the tile's dS: every SIMD runs the
+//    same 80 MFMAs per iteration and no dQ piece is ever summed across waves;
+//  * with two key blocks the first block's dQ piece goes to an fp32
+//    workspace in the owning lane's own layout and the same lane adds it to
+//    its piece in the second sweep: a thread re-reads only its own stores
+//    (no fence, no atomics, a fixed summation order), and dQ is rounded to
+//    bf16 once;
+//  * delta = rowsum(dO * O) is formed from the staged dO chunk and the
+//    matching O chunk while the tile is parked in LDS.
+// Whole heads per workgroup: no K / V reuse across workgroups, so the grid
+// needs no XCD remap.
+__global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, float* __restrict__ ws) {
+  constexpr int D = 64, KS = D / 16, DT = D / 32, QT = 64, KB = 256, NT = 512;
+  constexpr int TILE_BYTES = QT * D * 2;
+  constexpr int STAGE = 2 * TILE_BYTES + 2 * QT * 4;  // Q, dO, -lse / c, -delta
+  constexpr int KIMG_BYTES = KB * D * 2, DS_BYTES = KB * QT * 2;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE + KIMG_BYTES + 2 * DS_BYTES];
+  unsigned char* const Kimg = smem + 2 * STAGE;
+  unsigned char* const dSimg = Kimg + KIMG_BYTES;
+  // the wave index as a scalar: what derives from it (the key block row, the
+  // dQ piece, the mask test) stays out of the vector registers
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), h = lane >> 5;
+  const int bh = blockIdx.x, b = bh / P.H, hh = bh % P.H;
+  const int n_q_tiles = (P.Sq + QT - 1) / QT;
+  const int n_kb = (P.Sk + KB - 1) / KB;
+  // this wave's piece of a dQ tile it owns: queries dq_q.., columns dq_d..
+  const int w4 = wave & 3, dq_par = wave >> 2, dq_q = (w4 & 1) * 32, dq_d = (w4 >> 1) * 32;
+  // staging role: thread -> (row, 16-B chunk) of a 64 x 64 tile
+  const int srow = threadIdx.x >> 3, sch = threadIdx.x & 7;
+
+  TileLoader<D, QT, NT> ql, dl, ol;
+  // raw values are kept until the park point (see the dK / dV kernel)
+  float nls = 0.f;
+  bool nok = false;
+  auto fetch = [&](int q0) {
+    ql.load(P.q, b, hh, q0, P.Sq);
+    dl.load(P.dout, b, hh, q0, P.Sq);
+    ol.load(P.o, b, hh, q0, P.Sq);
+    nok = q0 + srow < P.Sq;
+    if (nok && sch == 0) nls = P.lse[static_cast<int64_t>(bh) * P.Sq + q0 + srow];
+  };
+  auto park = [&](unsigned char* stage) {
+    ql.store(stage);
+    dl.store(stage + TILE_BYTES);
+    float part = 0.f;  // rows past Sq loaded as zeros
+#pragma unroll
+    for (int e = 0; e < 8; ++e) part += bf2f(ol.reg[0][e]) * bf2f(dl.reg[0][e]);
+#pragma unroll
+    for (int o = 1; o < 8; o <<= 1) part += __shfl_xor(part, o, 64);
+    if (sch == 0) {
+      float* ls = reinterpret_cast<float*>(stage + 2 * TILE_BYTES);
+      ls[srow] = nok ? -nls * P.inv_scale_log2 : -INFINITY;
+      ls[QT + srow] = -part;
+    }
+  };
+
+  for (int kb = 0; kb < n_kb; ++kb) {
+    const int k_blk = kb * KB;
+    const int kl_ = wave * 32 + (lane & 31);  // key row inside the block
+    const int kw = k_blk + wave * 32, key = k_blk + kl_;
+    const bool k_ok = key < P.Sk;
+    const bool last_kb = kb == n_kb - 1;
+    // V rows stay in registers as B operands (lane holds row `key`, d =
+    // 16 ks + 8 h ..); the K rows are re-read from the K image per subtile:
+    // holding both left no room for the prefetched fragments at 256 VGPRs
+    bf16x8 vf[KS];
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      vf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.v.p + b * P.v.sb + static_cast<int64_t>(key) * P.v.ss +
+                                                       hh * P.v.sh + ks * 16 + 8 * h)
+                    : bf16x8{};
+    }
+    {
+      // K image of the block: 4 rows per thread, 64 apart.  The row index is
+      // made opaque so that the row pointers are formed here, per sweep: as
+      // sweep invariants they were hoisted above the sweep loop and spilled
+      // across the tile loop.
+      int r0 = srow;
+      asm volatile("" : "+v"(r0));
+      const bf16* kp = P.k.p + b * P.k.sb + static_cast<int64_t>(k_blk + r0) * P.k.ss + hh * P.k.sh + sch * 8;
+      bf16x8 kr[KB / 64];
+#pragma unroll
+      for (int i = 0; i < KB / 64; ++i)
+        kr[i] = k_blk + r0 + 64 * i < P.Sk ? *reinterpret_cast<const bf16x8*>(kp + 64 * i * P.k.ss) : bf16x8{};
+      int q0 = 0;  // opaque for the same reason: tile 0's fetch shares the tile loop's address form
+      asm volatile("" : "+s"(q0));
+      fetch(q0);
+#pragma unroll
+      for (int i = 0; i < KB / 64; ++i) *reinterpret_cast<bf16x8*>(Kimg + lds_off<D>(r0 + 64 * i, sch)) = kr[i];
+    }
+    park(smem);
+    __syncthreads();
+
+    f32x16 dk[DT], dv[DT];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) dk[dt] = dv[dt] = f32x16{};
+
+    // dQ^T piece of tile t from the published dS^T image and the K image
+    auto dq_tile = [&](int t) {
+      const unsigned char* dS = dSimg + (t & 1) * DS_BYTES;
+      float* wp = ws + ((static_cast<int64_t>(bh) * n_q_tiles + t) * 4 + w4) * 1024 + lane * 4;
+      f32x16 acc[1] = {f32x16{}};
+      // tr_frag_nat of both images, 16 keys per step: the swizzle repeats
+      // every 16 rows, so a step is base + 2 KiB and the four lane offsets
+      // are computed once
+      const int i16 = lane & 15, colq = 16 * ((lane >> 4) & 1) + 4 * (i16 & 3), ra = 8 * h + (i16 >> 2);
+      const int ck = dq_d + colq, cs = dq_q + colq;
+      const unsigned char* ka = Kimg + img_off<D * 2>(ra, ck >> 3) + (ck & 7) * 2;
+      const unsigned char* kb_ = Kimg + img_off<D * 2>(ra + 4, ck >> 3) + (ck & 7) * 2;
+      const unsigned char* sa = dS + img_off<QT * 2>(ra, cs >> 3) + (cs & 7) * 2;
+      const unsigned char* sb = dS + img_off<QT * 2>(ra + 4, cs >> 3) + (cs & 7) * 2;
+      auto product = [&] {
+        prio_hi(P);
+#pragma unroll 4
+        for (int k0 = 0; k0 < KB; k0 += 16) {
+          const int o = k0 * 128;
+          acc[0] = mfma32(cat44(lds_tr(ka, o), lds_tr(kb_, o)), cat44(lds_tr(sa, o), lds_tr(sb, o)), acc[0]);
+        }
+        prio_lo(P);
+      };
+      if (kb > 0) {
+        // the first sweep's piece: requested ahead of the MFMAs that cover its
+        // latency, added after them.  Load, product and add share one branch:
+        // with the load and the add under separate tests the compiler saw a
+        // path on which the load was never waited for, and made the next
+        // tile's first LDS reads wait for every global load in flight, the
+        // tile loads just issued among them.
+        f32x4 prev[4];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) prev[g] = *reinterpret_cast<const f32x4*>(wp + g * 256);
+        product();
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) acc[0][4 * g + e] += prev[g][e];
+      } else {
+        product();
+      }
+      if (last_kb) {
+        const int q = t * QT + dq_q + (lane & 31);
+        bf16* row = P.dq + b * P.dq_sb + static_cast<int64_t>(q) * P.dq_ss + hh * P.dq_sh + dq_d;
+        store_rows16<1>(row, acc, P.scale, h, q < P.Sq);
+      } else {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          f32x4 w;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) w[e] = acc[0][4 * g + e];
+          *reinterpret_cast<f32x4*>(wp + g * 256) = w;
+        }
+      }
+    };
+
+    // one extra trip: dQ of a tile is formed one iteration behind its dS.  Its
+    // barrier also ends the sweep: the next one overwrites the K image, stage
+    // 0 and dS image 0
+    for (int t = 0; t <= n_q_tiles; ++t) {
+      const int q0 = t * QT;
+      unsigned char* stage = smem + (t & 1) * STAGE;
+      const unsigned char* Qt = stage;
+      const unsigned char* Dt = stage + TILE_BYTES;
+      const float* ls = reinterpret_cast<const float*>(stage + 2 * TILE_BYTES);
+      const float* ds = ls + QT;
+      unsigned char* dSw = dSimg + (t & 1) * DS_BYTES;
+      // unconditional, like the park below (rows past Sq load as zeros
+      // without touching memory): under a `has next tile` test the compiler
+      // kept a path from these loads round the park's wait to the top of the
+      // loop and waited there for vmcnt(0), i.e. for the dQ stores
+      fetch(q0 + QT);
+      const bool need_mask = (q0 + QT > P.Sq) || (kw + 31 >= P.Sk);
+      if (t < n_q_tiles) {
+#pragma unroll
+        for (int qt = 0; qt < 2; ++qt) {
+          // every LDS fragment of the subtile is requested ahead of the MFMAs
+          // that consume it (the dK / dV kernel's PF form)
+          f32x16 s, dp;
+          bf16x8 qa[KS], da[KS], kf[KS], tda[2][DT], tqa[2][DT];
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) {
+            const int off = lds_off<D>(qt * 32 + (lane & 31), 2 * ks + h);
+            qa[ks] = lds_read16(Qt, off);
+            da[ks] = lds_read16(Dt, off);
+            kf[ks] = lds_read16(Kimg, lds_off<D>(kl_, 2 * ks + h));
+          }
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int ql_ = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            s[r] = ls[ql_];
+            dp[r] = ds[ql_];
+          }
+          prio_hi(P);
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) {
+            s = mfma32(qa[ks], kf[ks], s);
+            dp = mfma32(da[ks], vf[ks], dp);
+          }
+#pragma unroll
+          for (int dt = 0; dt < DT; ++dt) {
+            tda[0][dt] = tr_frag<D>(Dt, qt * 32, dt, lane);
+            tqa[0][dt] = tr_frag<D>(Qt, qt * 32, dt, lane);
+          }
+          prio_lo(P);
+          if (need_mask) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int qq = q0 + qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+              float pv = fexp2(s[r] * P.scale_log2);
+              if (qq >= P.Sq || !k_ok) pv = 0.f;
+              s[r] = pv;
+              dp[r] = pv * dp[r];
+            }
+          } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const float pv = fexp2(s[r] * P.scale_log2);
+              s[r] = pv;
+              dp[r] = pv * dp[r];
+            }
+          }
+          prio_hi(P);
+#pragma unroll
+          for (int st = 0; st < 2; ++st) {
+            const bf16x8 pf = acc_to_frag(s, st), sf = acc_to_frag(dp, st);
+            if (st == 0) {  // the second half's fragments arrive under the first half's MFMAs
+#pragma unroll
+              for (int dt = 0; dt < DT; ++dt) {
+                tda[1][dt] = tr_frag<D>(Dt, qt * 32 + 16, dt, lane);
+                tqa[1][dt] = tr_frag<D>(Qt, qt * 32 + 16, dt, lane);
+              }
+            }
+            // dS^T[key][query]: registers 4g..4g+3 are queries 8g + 4h + 0..3
+#pragma unroll
+            for (int g2 = 0; g2 < 2; ++g2) {
+              bf16x4 w;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) w[e] = sf[4 * g2 + e];
+              *reinterpret_cast<bf16x4*>(dSw + img_off<QT * 2>(kl_, qt * 4 + 2 * st + g2) + 8 * h) = w;
+            }
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) {
+              dv[dt] = mfma32(tda[st][dt], pf, dv[dt]);
+              dk[dt] = mfma32(tqa[st][dt], sf, dk[dt]);
+            }
+          }
+          prio_lo(P);
+        }
+      }
+      // park first: its wait for the tile loads would also wait out the dQ
+      // stores (vmcnt counts stores), which now drain under the next tile
+      park(smem + ((t + 1) & 1) * STAGE);
+      if (t > 0 && ((t - 1) & 1) == dq_par) dq_tile(t - 1);
+      __syncthreads();
+    }
+
+    bf16* krow = P.dk + b * P.dk_sb + static_cast<int64_t>(key) * P.dk_ss + hh * P.dk_sh;
+    bf16* vrow = P.dv + b * P.dv_sb + static_cast<int64_t>(key) * P.dv_ss + hh * P.dv_sh;
+    store_rows16<DT>(krow, dk, P.scale, h, k_ok);
+    store_rows16<DT>(vrow, dv, 1.f, h, k_ok);
+  }
+}
+
+// ===========================================================================
 static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale) {
   AttnParams P{};
   auto tv = [](const AttnTensors::T& x) {
@@ -1056,9 +1335,31 @@ static void launch_dkdv(int nkt, dim3 grid, dim3 block, hipStream_t st, const At
   hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1>), grid, block, 0, st, P);
 }
 
-void attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
-                   hipStream_t st) {
+// The one-pass kernel's shapes; both switches are read per call (the A/B tool
+// and the tests flip them inside one process).  FFK_ATTN_BWD_FUSED_DELTA=0
+// asks for the three-launch path and so also rules the one-pass kernel out.
+static bool onepass_eligible(int Sk, int D, bool causal, bool dbias) {
+  if (D != 64 || causal || Sk > 512 || dbias) return false;
+  const char* oe = getenv("FFK_ATTN_BWD_ONEPASS");
+  const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
+  return (oe ? atoi(oe) != 0 : true) && (fde ? atoi(fde) != 0 : true);
+}
+
+int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias) {
+  if (!onepass_eligible(Sk, D, causal, dbias) || Sk <= 256) return 0;
+  return static_cast<int64_t>(B) * H * ((Sq + 63) / 64) * 64 * 64;
+}
+
+int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
+                  hipStream_t st, float* ws) {
   AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
+  // a second key block needs the workspace: callers that pass none keep the
+  // two-kernel path
+  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv) && (Sk <= 256 || ws)) {
+    hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(static_cast<unsigned>(B * H)), dim3(512), 0, st, P, ws);
+    FFK_LAUNCH_CHECK("attention_bwd");
+    return 1;
+  }
   const int64_t rows = static_cast<int64_t>(B) * H * Sq;
   const int tpr = D / 8;
   dim3 gd(static_cast<unsigned>((rows * tpr + 255) / 256));
@@ -1096,6 +1397,7 @@ void attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
   }
 #undef FFK_ATTN_BWD
   FFK_LAUNCH_CHECK("attention_bwd");
+  return 0;
 }
 
 }  // namespace ffk

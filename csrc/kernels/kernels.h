@@ -92,8 +92,14 @@ struct AttnTensors {
 };
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st);
-void attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
-                   hipStream_t st);
+// Returns the path that ran: 1 = the one-pass kernel (D = 64, non-causal,
+// Sk <= 512, no dbias; FFK_ATTN_BWD_ONEPASS=0 turns it off), 0 = the dQ and
+// dK/dV kernels.  With Sk > 256 the one-pass kernel needs `ws`, an fp32
+// scratch of attention_bwd_workspace() floats (0: the call is not eligible
+// or needs none).
+int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias);
+int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
+                  hipStream_t st, float* ws = nullptr);
 
 // ---- gemm.hip (bf16 MFMA GEMM with fused epilogues)
 // C[M,N] = act(alpha * op(A)[M,K] @ op(B)[K,N] + bias[N]) (+ beta*C)

@@ -440,8 +440,15 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
             slab = torch.empty(B * max(nq, nk), 3 * HD, device=q.device, dtype=torch.float32)
             ld = 3 * HD
             dbs = [slab.data_ptr() + 4 * i * HD if t is not None else 0 for i, t in enumerate(dbias)]
-    ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk), _view4(dv),
-                        lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal), _stream(), *dbs, ld)
+    # the one-pass kernel (D = 64, non-causal, Sk <= 512, no dbias) keeps the
+    # first key block's dQ in an fp32 scratch when there is a second one
+    n_ws = ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal), dbias is not None)
+    ws = torch.empty(n_ws, device=q.device, dtype=torch.float32) if n_ws else None
+    path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
+                               _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
+                               _stream(), *dbs, ld, _p(ws))
+    if path == 1:
+        STATS["attention_bwd_onepass"] += 1
     if slab is not None:
         # every (row block, column) of the slab was written once; rows past a
         # tensor's own row-block count (Sq != Sk) are not part of its sum

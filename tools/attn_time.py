@@ -4,7 +4,7 @@ and GPT-3-medium shapes; FF_PKG_ROOT selects the package tree (same-box A/B of
 two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
 
     python tools/attn_time.py [iters]
-    python tools/attn_time.py --pipe-ab | --delta-ab   (same-process A/B of a kernel switch)
+    python tools/attn_time.py --pipe-ab | --delta-ab | --onepass-ab   (same-process A/B of a kernel switch)
 """
 import json
 import os
@@ -16,7 +16,9 @@ import torch  # noqa: E402
 
 from flexflow_train_amd import kernels as K  # noqa: E402
 
-SHAPES = {"bert-large": (64, 512, 16, 64, False), "gpt3-medium": (16, 2048, 16, 64, True)}   # bench batches
+SHAPES = {"bert-large": (64, 512, 16, 64, False), "gpt3-medium": (16, 2048, 16, 64, True),
+          # the shipped bench batches
+          "bert-large-b128": (128, 512, 16, 64, False), "gpt3-medium-b32": (32, 2048, 16, 64, True)}
 
 
 def _time(fn, iters):
@@ -56,7 +58,9 @@ def env_ab(var, which, iters, rounds=5):
         med = {p: statistics.median(v) for p, v in t.items()}
         print(json.dumps({"shape": name, "switch": var, "pass": which, "ms_0": round(med[0], 4),
                           "ms_1": round(med[1], 4), "tflops_0": round(fl / med[0] / 1e9, 1),
-                          "tflops_1": round(fl / med[1] / 1e9, 1)}), flush=True)
+                          "tflops_1": round(fl / med[1] / 1e9, 1),
+                          "rounds_0": [round(x, 4) for x in t[0]], "rounds_1": [round(x, 4) for x in t[1]]}),
+              flush=True)
     os.environ.pop(var, None)
 
 
@@ -75,8 +79,11 @@ def pmc_run(n=5):
             for _ in range(n):
                 K.attention_fwd(q, k, v, causal=causal, out=o)
         os.environ.pop("FFK_ATTN_FWD_PIPE", None)
-        for _ in range(n):
-            K.attention_bwd(q, k, v, o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], causal=causal)
+        for p in ("0", "1"):   # the dQ + dK/dV kernels, then the one-pass kernel where it applies
+            os.environ["FFK_ATTN_BWD_ONEPASS"] = p
+            for _ in range(n):
+                K.attention_bwd(q, k, v, o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], causal=causal)
+        os.environ.pop("FFK_ATTN_BWD_ONEPASS", None)
         torch.cuda.synchronize()
         print(name, "done", flush=True)
 
@@ -88,6 +95,8 @@ def main():
         return env_ab("FFK_ATTN_FWD_PIPE", "fwd", 50)
     if "--delta-ab" in sys.argv:       # delta fused into the dQ kernel
         return env_ab("FFK_ATTN_BWD_FUSED_DELTA", "bwd", 30)
+    if "--onepass-ab" in sys.argv:     # one-pass backward (BERT shapes; the causal shapes are not eligible)
+        return env_ab("FFK_ATTN_BWD_ONEPASS", "bwd", 30)
     if "--wide-ab" in sys.argv:        # 16-B output row stores (forward / backward epilogues)
         env_ab("FFK_ATTN_WIDE_STORE", "fwd", 50)
         return env_ab("FFK_ATTN_WIDE_STORE", "bwd", 30)
