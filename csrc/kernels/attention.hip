@@ -31,6 +31,25 @@
 // Tensor addressing: every tensor is [B, S, H, D] with arbitrary strides for
 // b / s / h and contiguous d, so the fused QKV projection output
 // [B, S, 3, H, D] is consumed in place.  LSE is [B, H, S] fp32, log2 domain.
+//
+// Attention dropout (DROP instantiations of the forward, dQ and dK/dV
+// kernels).  The keep / drop decision of probability (b, h, q, k) is a pure
+// function of (seed, b, h, q, k, T), independent of tiling, kernel, wave
+// layout and strides; every kernel regenerates it and nothing of size
+// Sq x Sk is stored.  The definition (ops/attention.py attention_dropout_mask
+// is its second implementation):
+//   seed_eff = seed + *seed_dev (mod 2^64; seed alone without a device word)
+//   key      = hash_u32(seed_eff, b * H + h)      splitmix64 finaliser, low 32
+//                                                 bits; once per workgroup
+//   x        = mix32((q * Sk + k) ^ key)          needs Sq * Sk < 2^32
+//   mix32:     x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b;
+//              x ^= x >> 16
+//   keep iff (x >> 8) >= T,  T = round(p * 2^24) from the host
+// Kept probabilities are scaled by rs = 2^24 / (2^24 - T), exactly unbiased
+// for the realised rate.  m, l and the LSE come from the undropped
+// probabilities (the LSE is that of a p = 0 call); O = rs (keep . P) V, so
+// delta = rowsum(dO * O) is unchanged and dS = P (keep rs dP - delta),
+// dV = rs (keep . P)^T dO.
 #include <cstdlib>
 
 #include "kernels.h"
@@ -59,7 +78,29 @@ struct AttnParams {
   int prio;          // raise wave priority around MFMA clusters (FFK_ATTN_PRIO; guide T5)
   int xcd;           // XCD-local head order of non-causal grids (FFK_ATTN_XCD, default on)
   int wide_store;    // 16-B output rows via permlane32_swap (FFK_ATTN_WIDE_STORE, default on)
+  // attention dropout (DROP kernels only; appended so the other fields keep their offsets)
+  unsigned drop_thr;        // T << 8: a probability is dropped iff its hash word is below this
+  float drop_rs;            // keep scale 2^24 / (2^24 - T)
+  uint64_t seed;
+  const int64_t* seed_dev;  // optional device-resident addend of the seed
 };
+
+// Dropout hash (definition in the header comment).  drop_key is uniform over
+// the workgroup: made a scalar so the per-element xor takes it from an SGPR.
+__device__ __forceinline__ unsigned drop_key(const AttnParams& P, int bh) {
+  uint64_t seed = P.seed;
+  if (P.seed_dev) seed += static_cast<uint64_t>(*P.seed_dev);
+  return __builtin_amdgcn_readfirstlane(hash_u32(seed, static_cast<uint64_t>(bh)));
+}
+__device__ __forceinline__ bool dropped(unsigned idx, unsigned key, unsigned thr) {
+  unsigned x = idx ^ key;
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x < thr;  // (x >> 8) < T
+}
 
 // Store a wave's 32-row C^T tile (lane & 31 -> row, registers -> d) as rows
 // of bf16, 16 bytes per store.  A lane holds 4 consecutive d of each 8-group
@@ -219,7 +260,10 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 
 // ===========================================================================
 // Forward
-template <int D, bool CAUSAL>
+// DROP: the dropped probabilities are zeroed after the row sum is taken, so
+// m, l and the LSE are those of the undropped softmax; the keep scale is
+// folded into the epilogue's 1 / l.
+template <int D, bool CAUSAL, bool DROP = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   constexpr int KS = D / 16;        // k-steps over the head dim
   constexpr int DT = D / 32;        // 32-wide output tiles over the head dim
@@ -251,6 +295,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) o[dt] = f32x16{};
   float m = -INFINITY, l = 0.f;
+  // dropout: hash index of s[kt][r] = drow + k0 + kt * 32 + (r & 3) + 8 * (r >> 2)
+  [[maybe_unused]] unsigned dkey = 0, drow = 0;
+  if constexpr (DROP) {
+    dkey = drop_key(P, bh);
+    drow = static_cast<unsigned>(q) * static_cast<unsigned>(P.Sk) + 4u * h;
+  }
 
   int n_tiles = (P.Sk + KV - 1) / KV;
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
@@ -333,6 +383,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
           psum[kt] += pv;
         }
       l += psum[0] + psum[1];
+      if constexpr (DROP) {
+        const unsigned dt0 = drow + static_cast<unsigned>(k0);
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (dropped(dt0 + (kt * 32 + (r & 3) + 8 * (r >> 2)), dkey, P.drop_thr)) s[kt][r] = 0.f;
+      }
       // ---- O^T[d][q] += V^T[d][key] P^T[key][q]
       prio_hi(P);
 #pragma unroll
@@ -358,7 +416,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 
   // ---- epilogue: O = O^T / l, LSE
   const float lt = l + __shfl_xor(l, 32, 64);
-  const float inv = lt > 0.f ? 1.f / lt : 0.f;
+  float inv = lt > 0.f ? 1.f / lt : 0.f;
+  if constexpr (DROP) inv *= P.drop_rs;
   bf16* orow = P.o_out + b * P.o_sb + static_cast<int64_t>(q) * P.o_ss + hh * P.o_sh;
   if (P.wide_store) {
     store_rows16<DT>(orow, o, inv, h, q_ok);
@@ -570,8 +629,10 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(AttnParams P) {
 // here from the dO fragments already in registers (plus one 16-B O load per
 // fragment) and written out for the dK / dV kernel, which then runs AFTER
 // this one — the separate delta pass (a full re-read of dO and O) goes away.
-template <int D, bool CAUSAL, bool FUSED_DELTA = false>
-__global__ __launch_bounds__(256, (D == 64 ? (CAUSAL ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
+// DROP: dS^T = P^T (keep rs dP^T - delta); same (lane -> query, register ->
+// key) coordinates as the forward.
+template <int D, bool CAUSAL, bool FUSED_DELTA = false, bool DROP = false>
+__global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, KV = 64;
   constexpr int TILE_BYTES = KV * D * 2;
   __shared__ __attribute__((aligned(16))) unsigned char smem[4 * TILE_BYTES];
@@ -619,6 +680,20 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL ? 2 : 3) : 1)) void attn_bw
   f32x16 dq[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x16{};
+  [[maybe_unused]] unsigned dkey = 0, drow = 0;
+  if constexpr (DROP) {
+    dkey = drop_key(P, bh);
+    drow = static_cast<unsigned>(q) * static_cast<unsigned>(P.Sk) + 4u * h;
+  }
+  // dP of register r with the dropout keep scale applied (DROP only)
+  auto kept = [&](float dpv, int k0, int kt, int r) -> float {
+    if constexpr (DROP) {
+      const unsigned idx = drow + static_cast<unsigned>(k0) + (kt * 32 + (r & 3) + 8 * (r >> 2));
+      return dpv * (dropped(idx, dkey, P.drop_thr) ? 0.f : P.drop_rs);
+    } else {
+      return dpv;
+    }
+  };
 
   int n_tiles = (P.Sk + KV - 1) / KV;
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
@@ -659,11 +734,11 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL ? 2 : 3) : 1)) void attn_bw
             const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             float pv = fexp2(s[r] * P.scale_log2 - lse);
             if (key >= P.Sk || (CAUSAL && key > q) || !q_ok) pv = 0.f;
-            s[r] = pv * (dp[r] - dlt);  // dS^T
+            s[r] = pv * (kept(dp[r], k0, kt, r) - dlt);  // dS^T
           }
         } else {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) s[r] = fexp2(s[r] * P.scale_log2 - lse) * (dp[r] - dlt);
+          for (int r = 0; r < 16; ++r) s[r] = fexp2(s[r] * P.scale_log2 - lse) * (kept(dp[r], k0, kt, r) - dlt);
         }
         prio_hi(P);
 #pragma unroll
@@ -712,9 +787,14 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL ? 2 : 3) : 1)) void attn_bw
 // NKT = 2 (64 keys per wave): every Q / dO fragment read from LDS feeds two
 // key subtiles, halving LDS traffic per MFMA; slower in practice (register
 // pressure -> 1 wave/SIMD), kept behind FFK_ATTN_BWD_NKT=2 for experiments.
-template <int D, bool CAUSAL, int NKT, bool PF = false>
+// DROP (NKT = 1): the key is on the lane and the queries are in the
+// registers, so the hash index q * Sk + key steps by Sk per register; the dP
+// accumulator starts from zero and -delta is added after the keep scale
+// (dS = P (keep rs dP - delta)); dV takes keep . P and rs at the store.
+template <int D, bool CAUSAL, int NKT, bool PF = false, bool DROP = false>
 __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
   static_assert(!PF || NKT == 1, "PF prefetch is written for one key subtile per wave");
+  static_assert(!DROP || NKT == 1, "dropout is written for one key subtile per wave");
   constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32 * NKT;
   constexpr int TILE_BYTES = QT * D * 2;
   constexpr int STAGE = 2 * TILE_BYTES + 2 * QT * 4;  // Q, dO, lse, delta
@@ -755,6 +835,13 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
 
   const int n_q_tiles = (P.Sq + QT - 1) / QT;
   const int t0 = CAUSAL ? (k_blk / QT) : 0;
+  // dropout: hash index of register r of a subtile = (first query + 4 h +
+  // (r & 3) + 8 (r >> 2)) * Sk + key
+  [[maybe_unused]] unsigned dkey = 0, dcol = 0;
+  if constexpr (DROP) {
+    dkey = drop_key(P, bh);
+    dcol = 4u * h * static_cast<unsigned>(P.Sk) + static_cast<unsigned>(key[0]);
+  }
 
   TileLoader<D, QT> ql, dl;
   // row constants of a query tile, pre-shaped to seed the S and dP
@@ -815,6 +902,14 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
     const bool wave_active = !CAUSAL || (q0 + QT - 1 >= kw);
     const bool need_mask = (q0 + QT > P.Sq) || (CAUSAL && q0 < kw + KW - 1) || (kw + KW - 1 >= P.Sk);
     if (wave_active) {
+      // DROP at D = 128 (all 512 registers in use): the fragment offsets of
+      // the per-pair reads are derived from the lane id again in every tile.
+      // As loop invariants some of them were spilled in the causal form and
+      // reloaded in the loop, each reload with a vmcnt(0) wait that also
+      // drains the next tile's prefetch.
+      int ln = lane;
+      if constexpr (DROP && D == 128) asm volatile("" : "+v"(ln));
+      const int hl = ln >> 5;
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         f32x16 s[NKT], dp[NKT];
@@ -839,7 +934,7 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
           for (int r = 0; r < 16; ++r) {
             const int ql_ = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             s[j][r] = ls[ql_];
-            dp[j][r] = ds[ql_];
+            dp[j][r] = DROP ? 0.f : ds[ql_];
           }
         prio_hi(P);
         if constexpr (PF) {
@@ -858,7 +953,7 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
         } else {
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            const int off = lds_off<D>(qt * 32 + (lane & 31), 2 * ks + h);
+            const int off = lds_off<D>(qt * 32 + (ln & 31), 2 * ks + hl);
             const bf16x8 qa = lds_read16(Qt, off), da = lds_read16(Dt, off);
 #pragma unroll
             for (int j = 0; j < NKT; ++j) {
@@ -870,7 +965,20 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
         prio_lo(P);
 #pragma unroll
         for (int j = 0; j < NKT; ++j) {
-          if (need_mask) {
+          if constexpr (DROP) {
+            const unsigned dq0 = static_cast<unsigned>(q0 + qt * 32) * static_cast<unsigned>(P.Sk) + dcol;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int rq = (r & 3) + 8 * (r >> 2);
+              const int qq = q0 + qt * 32 + rq + 4 * h;
+              float pv = fexp2(s[j][r] * P.scale_log2);
+              if (need_mask && (qq >= P.Sq || (CAUSAL && key[j] > qq) || !k_ok[j])) pv = 0.f;
+              const bool drop =
+                  dropped(dq0 + static_cast<unsigned>(rq) * static_cast<unsigned>(P.Sk), dkey, P.drop_thr);
+              dp[j][r] = pv * fmaf(drop ? 0.f : P.drop_rs, dp[j][r], ds[qt * 32 + rq + 4 * h]);
+              s[j][r] = drop ? 0.f : pv;
+            }
+          } else if (need_mask) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int qq = q0 + qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
@@ -904,8 +1012,8 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
               da = tda_pf[st][dt];
               qa = tqa_pf[st][dt];
             } else {
-              da = tr_frag<D>(Dt, qt * 32 + 16 * st, dt, lane);
-              qa = tr_frag<D>(Qt, qt * 32 + 16 * st, dt, lane);
+              da = tr_frag<D>(Dt, qt * 32 + 16 * st, dt, ln);
+              qa = tr_frag<D>(Qt, qt * 32 + 16 * st, dt, ln);
             }
 #pragma unroll
             for (int j = 0; j < NKT; ++j) {
@@ -925,16 +1033,18 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
     }
     __syncthreads();
   }
+  float vmul = 1.f;  // dV's store scale: the dropout keep scale
+  if constexpr (DROP) vmul = P.drop_rs;
 #pragma unroll
   for (int j = 0; j < NKT; ++j) {
     if (P.db_ld) {
       if (kw + 32 * j >= P.Sk) continue;
       const int64_t roff = (static_cast<int64_t>(b) * ((P.Sk + 31) / 32) + (kw + 32 * j) / 32) * P.db_ld + hh * D;
       if (P.dbk) bias_partial<DT>(dk[j], P.scale, P.dbk + roff, lane);
-      if (P.dbv) bias_partial<DT>(dv[j], 1.f, P.dbv + roff, lane);
+      if (P.dbv) bias_partial<DT>(dv[j], vmul, P.dbv + roff, lane);
     } else {
       if (P.dbk) bias_colsum<DT>(dk[j], P.scale, P.dbk + hh * D, lane);
-      if (P.dbv) bias_colsum<DT>(dv[j], 1.f, P.dbv + hh * D, lane);
+      if (P.dbv) bias_colsum<DT>(dv[j], vmul, P.dbv + hh * D, lane);
     }
   }
 #pragma unroll
@@ -943,7 +1053,7 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
     bf16* vrow = P.dv + b * P.dv_sb + static_cast<int64_t>(key[j]) * P.dv_ss + hh * P.dv_sh;
     if (P.wide_store) {   // every lane swaps; k_ok guards the stores
       store_rows16<DT>(krow, dk[j], P.scale, h, k_ok[j]);
-      store_rows16<DT>(vrow, dv[j], 1.f, h, k_ok[j]);
+      store_rows16<DT>(vrow, dv[j], vmul, h, k_ok[j]);
       continue;
     }
     if (!k_ok[j]) continue;
@@ -955,7 +1065,7 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           a[e] = f2bf(dk[j][dt][4 * g4 + e] * P.scale);
-          c[e] = f2bf(dv[j][dt][4 * g4 + e]);
+          c[e] = f2bf(DROP ? dv[j][dt][4 * g4 + e] * vmul : dv[j][dt][4 * g4 + e]);
         }
         *reinterpret_cast<bf16x4*>(krow + dt * 32 + 8 * g4 + 4 * h) = a;
         *reinterpret_cast<bf16x4*>(vrow + dt * 32 + 8 * g4 + 4 * h) = c;
@@ -1281,6 +1391,15 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
   P.xcd = xe ? atoi(xe) : 1;
   const char* we = getenv("FFK_ATTN_WIDE_STORE");
   P.wide_store = we ? atoi(we) : 1;
+  if (t.drop_threshold) {
+    if (t.drop_threshold >= (1u << 24)) throw std::invalid_argument("attention: dropout threshold must be below 2^24");
+    if (static_cast<uint64_t>(Sq) * static_cast<uint64_t>(Sk) >= (1ull << 32))
+      throw std::invalid_argument("attention: dropout needs Sq * Sk < 2^32");
+    P.drop_thr = t.drop_threshold << 8;
+    P.drop_rs = t.drop_keep_scale;
+    P.seed = t.seed;
+    P.seed_dev = t.seed_dev;
+  }
   return P;
 }
 
@@ -1296,6 +1415,19 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
   // in-wave overlap gains
   const char* pe = getenv("FFK_ATTN_FWD_PIPE");
   const int pipe = pe ? atoi(pe) : 0;
+  if (P.drop_thr) {  // dropout: the default variant only, whatever the experimental switches say
+    if (D == 64) {
+      if (causal) hipLaunchKernelGGL((attn_fwd_kernel<64, true, true>), grid, block, 0, st, P);
+      else hipLaunchKernelGGL((attn_fwd_kernel<64, false, true>), grid, block, 0, st, P);
+    } else if (D == 128) {
+      if (causal) hipLaunchKernelGGL((attn_fwd_kernel<128, true, true>), grid, block, 0, st, P);
+      else hipLaunchKernelGGL((attn_fwd_kernel<128, false, true>), grid, block, 0, st, P);
+    } else {
+      throw std::invalid_argument("attention: head dim must be 64 or 128");
+    }
+    FFK_LAUNCH_CHECK("attention_fwd");
+    return;
+  }
   if (pipe && D == 64) {
     if (causal) hipLaunchKernelGGL((attn_fwd_pipe_kernel<64, true>), grid, block, 0, st, P);
     else hipLaunchKernelGGL((attn_fwd_pipe_kernel<64, false>), grid, block, 0, st, P);
@@ -1314,9 +1446,9 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
   FFK_LAUNCH_CHECK("attention_fwd");
 }
 
-template <int D, bool CAUSAL>
+template <int D, bool CAUSAL, bool DROP = false>
 static void launch_dkdv(int nkt, dim3 grid, dim3 block, hipStream_t st, const AttnParams& P) {
-  if constexpr (D == 64) {
+  if constexpr (D == 64 && !DROP) {
     if (nkt == 2) {
       hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 2>), grid, block, 0, st, P);
       return;
@@ -1328,18 +1460,23 @@ static void launch_dkdv(int nkt, dim3 grid, dim3 block, hipStream_t st, const At
     const char* e = getenv("FFK_ATTN_BWD_PF");
     return e ? atoi(e) : 1;
   }();
-  if (pf && D == 64) {  // at D = 128 (one wave / SIMD) the prefetch registers spill
-    hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, D == 64>), grid, block, 0, st, P);
-    return;
+  // at D = 128 (one wave / SIMD) the prefetch registers spill; so they do with
+  // dropout at D = 64 (256 registers with no room for the hash: 40 - 72 bytes
+  // of scratch, reloaded in the loop), which takes the per-pair reads
+  if constexpr (!DROP) {
+    if (pf && D == 64) {
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, D == 64>), grid, block, 0, st, P);
+      return;
+    }
   }
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1>), grid, block, 0, st, P);
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, false, DROP>), grid, block, 0, st, P);
 }
 
 // The one-pass kernel's shapes; both switches are read per call (the A/B tool
 // and the tests flip them inside one process).  FFK_ATTN_BWD_FUSED_DELTA=0
 // asks for the three-launch path and so also rules the one-pass kernel out.
-static bool onepass_eligible(int Sk, int D, bool causal, bool dbias) {
-  if (D != 64 || causal || Sk > 512 || dbias) return false;
+static bool onepass_eligible(int Sk, int D, bool causal, bool dbias, bool drop = false) {
+  if (D != 64 || causal || Sk > 512 || dbias || drop) return false;
   const char* oe = getenv("FFK_ATTN_BWD_ONEPASS");
   const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
   return (oe ? atoi(oe) != 0 : true) && (fde ? atoi(fde) != 0 : true);
@@ -1355,7 +1492,7 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
   // a second key block needs the workspace: callers that pass none keep the
   // two-kernel path
-  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv) && (Sk <= 256 || ws)) {
+  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv, P.drop_thr != 0) && (Sk <= 256 || ws)) {
     hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(static_cast<unsigned>(B * H)), dim3(512), 0, st, P, ws);
     FFK_LAUNCH_CHECK("attention_bwd");
     return 1;
@@ -1370,7 +1507,8 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   // NKT = 2 (64 keys per wave) halves LDS reads per MFMA but needs ~500
   // registers (1 wave/SIMD, spills when causal): measured 0.24 vs 0.21 ms
   // (BERT shape) and 0.92 vs 0.56 ms (GPT causal) — opt-in only.
-  const int nkt = D == 64 && nkt_env == 2 ? 2 : 1;
+  // (dropout: the default variants only, NKT = 1 and the fused delta)
+  const int nkt = D == 64 && nkt_env == 2 && !P.drop_thr ? 2 : 1;
   const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nbh = static_cast<unsigned>(B * H);
   const unsigned nk = static_cast<unsigned>((Sk + 128 * nkt - 1) / (128 * nkt));
   dim3 gq = causal ? dim3(nbh, nq) : dim3(nq, nbh), gk = causal ? dim3(nbh, nk) : dim3(nk, nbh), block(256);
@@ -1378,7 +1516,10 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
   const bool fused_delta = fde ? atoi(fde) != 0 : true;
 #define FFK_ATTN_BWD(DD, CC)                                                          \
-  if (fused_delta) {                                                                  \
+  if (P.drop_thr) {                                                                   \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, true>), gq, block, 0, st, P);\
+    launch_dkdv<DD, CC, true>(nkt, gk, block, st, P);                                 \
+  } else if (fused_delta) {                                                           \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true>), gq, block, 0, st, P);      \
     launch_dkdv<DD, CC>(nkt, gk, block, st, P);                                       \
   } else {                                                                            \

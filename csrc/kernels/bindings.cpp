@@ -25,6 +25,16 @@ static AttnTensors::T tview(const py::tuple& t) {
   return r;
 }
 
+// attention dropout: threshold T = round(p * 2^24) (0 = off), keep scale 2^24 / (2^24 - T)
+static void set_dropout(AttnTensors& t, uint32_t drop_t, uint64_t seed, uintptr_t seed_dev) {
+  if (!drop_t) return;
+  if (drop_t >= (1u << 24)) throw std::invalid_argument("attention: dropout threshold must be below 2^24");
+  t.drop_threshold = drop_t;
+  t.drop_keep_scale = 16777216.f / static_cast<float>((1u << 24) - drop_t);
+  t.seed = seed;
+  t.seed_dev = reinterpret_cast<const int64_t*>(seed_dev);
+}
+
 PYBIND11_MODULE(_ffkernels, m) {
   m.doc() = "flexflow_train_amd gfx950 HIP kernels";
   m.attr("ARCH") = "gfx950";
@@ -132,19 +142,24 @@ PYBIND11_MODULE(_ffkernels, m) {
     embedding_bwd(dt, ib, P(idx), P(dout), F(dW), B, L, D, mode, n, F(ws), copies, S(st));
   });
   m.def("attention_fwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, uintptr_t lse, int B, int H, int Sq,
-                            int Sk, int D, float scale, bool causal, uintptr_t st) {
+                            int Sk, int D, float scale, bool causal, uintptr_t st, uint32_t drop_t, uint64_t seed,
+                            uintptr_t seed_dev) {
     AttnTensors t;
     t.q = tview(q);
     t.k = tview(k);
     t.v = tview(v);
     t.o = tview(o);
     t.lse = F(lse);
+    set_dropout(t, drop_t, seed, seed_dev);
     attention_fwd(t, B, H, Sq, Sk, D, scale, causal, S(st));
-  });
+  }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("B"), py::arg("H"),
+        py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"),
+        py::arg("drop_t") = 0, py::arg("seed") = 0, py::arg("seed_dev") = 0);
   m.def("attention_bwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, py::tuple dout, py::tuple dq,
                             py::tuple dk, py::tuple dv, uintptr_t lse, uintptr_t delta, int B, int H, int Sq, int Sk,
                             int D, float scale, bool causal, uintptr_t st, uintptr_t dbq, uintptr_t dbk,
-                            uintptr_t dbv, int64_t db_ld, uintptr_t ws) {
+                            uintptr_t dbv, int64_t db_ld, uintptr_t ws, uint32_t drop_t, uint64_t seed,
+                            uintptr_t seed_dev) {
     AttnTensors t;
     t.q = tview(q);
     t.k = tview(k);
@@ -160,11 +175,13 @@ PYBIND11_MODULE(_ffkernels, m) {
     t.dbk = F(dbk);
     t.dbv = F(dbv);
     t.db_ld = db_ld;
+    set_dropout(t, drop_t, seed, seed_dev);
     return attention_bwd(t, B, H, Sq, Sk, D, scale, causal, S(st), F(ws));
   }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("dq"), py::arg("dk"),
         py::arg("dv"), py::arg("lse"), py::arg("delta"), py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"), py::arg("dbq") = 0, py::arg("dbk") = 0,
-        py::arg("dbv") = 0, py::arg("db_ld") = 0, py::arg("ws") = 0);
+        py::arg("dbv") = 0, py::arg("db_ld") = 0, py::arg("ws") = 0, py::arg("drop_t") = 0, py::arg("seed") = 0,
+        py::arg("seed_dev") = 0);
   m.def("attention_bwd_workspace", &attention_bwd_workspace, py::arg("B"), py::arg("H"), py::arg("Sq"),
         py::arg("Sk"), py::arg("D"), py::arg("causal"), py::arg("dbias"));
   m.def("gemm", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre, int M, int N, int K,

@@ -89,6 +89,17 @@ struct AttnTensors {
   // floats; dq rows b * ceil(Sq/32) + q/32, dk / dv rows b * ceil(Sk/32) +
   // k/32, columns h * D + d) written without atomics; the caller sums rows
   int64_t db_ld = 0;
+  // attention dropout (definition: attention.hip header).  drop_threshold =
+  // round(p * 2^24), 0 = off; a probability is kept iff its 24-bit hash word
+  // is >= the threshold and then scaled by drop_keep_scale = 2^24 / (2^24 -
+  // threshold).  The hash seed is seed + *seed_dev (seed_dev: optional device
+  // word, so a captured launch draws a new mask per replay).  The forward
+  // and the backward of one call must be given the same values.  With
+  // dropout on, the backward is always the dQ + dK/dV kernel pair.
+  uint32_t drop_threshold = 0;
+  float drop_keep_scale = 1.f;
+  uint64_t seed = 0;
+  const int64_t* seed_dev = nullptr;
 };
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st);

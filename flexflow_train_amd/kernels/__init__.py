@@ -390,28 +390,69 @@ def _view4(t: torch.Tensor):
     return (t.data_ptr(), t.stride(0), t.stride(1), t.stride(2))
 
 
-def attention_fwd(q, k, v, causal=False, scale=None, out=None):
+def attention_dropout_threshold(p: float) -> int:
+    """The 24-bit integer threshold T = round(p * 2^24) of attention dropout
+    (0: off).  A probability is kept iff its hash word's top 24 bits are >= T
+    and then scaled by 2^24 / (2^24 - T)."""
+    p = float(p)
+    if not p < 1.0:
+        raise ValueError(f"attention: dropout probability must be below 1, got {p}")
+    if p <= 0.0:
+        return 0
+    T = int(round(p * (1 << 24)))
+    if T >= 1 << 24:
+        raise ValueError(f"attention: dropout probability {p} rounds to 1")
+    return T
+
+
+def _attn_dropout_args(p, seed, seed_dev, q, Sq, Sk):
+    """(threshold, seed mod 2^64, seed_dev pointer) of an attention call."""
+    T = attention_dropout_threshold(p)
+    if not T:
+        return 0, 0, 0
+    if Sq * Sk >= 1 << 32:
+        raise ValueError(f"attention: dropout needs Sq * Sk < 2^32, got {Sq} x {Sk}")
+    if seed_dev is not None:
+        if (not isinstance(seed_dev, torch.Tensor) or seed_dev.dtype != torch.int64 or seed_dev.numel() != 1
+                or seed_dev.device != q.device):
+            raise ValueError("attention: seed_dev must be a 1-element int64 tensor on the device of q")
+    STATS["attention_dropout"] += 1
+    return T, int(seed) & ((1 << 64) - 1), _p(seed_dev)
+
+
+def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None):
     """Flash attention forward.  q,k,v: [B, S, H, D] bf16 views (any b/s/h
     strides, e.g. slices of a packed [B, S, 3, H, D] QKV buffer).
-    Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain)."""
+    Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain).
+
+    ``dropout_p`` > 0: dropout on the attention probabilities inside the
+    kernel; the mask is that of ``ops.attention.attention_dropout_mask`` for
+    the seed ``seed + seed_dev[0]`` (``seed_dev``: optional 1-element int64
+    device tensor, read by the kernel, so a captured call follows it).  The
+    LSE is that of the undropped softmax."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     if D not in (64, 128):
         raise ValueError("attention: head dim must be 64 or 128")
     if k.shape != (B, Sk, H, D) or v.shape != (B, Sk, H, D):
         raise ValueError("attention: q/k/v shape mismatch")
+    drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
     if out is None:
         out = torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
     lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
     sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     ext().attention_fwd(_view4(q), _view4(k), _view4(v), _view4(out), lse.data_ptr(), B, H, Sq, Sk, D, sc,
-                        bool(causal), _stream())
+                        bool(causal), _stream(), *drop)
     STATS["attention_fwd"] += 1
     return out, lse
 
 
-def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False):
-    """Flash-attention backward into dq / dk / dv.  ``dbias`` = optional
+def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False,
+                  dropout_p=0.0, seed=0, seed_dev=None):
+    """Flash-attention backward into dq / dk / dv; returns the path that ran
+    (1: the one-pass kernel, 0: the dQ and dK/dV kernels).  ``dropout_p``,
+    ``seed``, ``seed_dev``: those of the forward call that produced ``o``
+    (dropout always takes path 0).  ``dbias`` = optional
     (dbq, dbk, dbv) fp32 [H*D] projection-bias gradients, accumulated with the
     column sums of dq / dk / dv (over batch and sequence) computed in the
     kernels' epilogues: by default each wave stores its 32-row partial into a
@@ -442,11 +483,12 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
             dbs = [slab.data_ptr() + 4 * i * HD if t is not None else 0 for i, t in enumerate(dbias)]
     # the one-pass kernel (D = 64, non-causal, Sk <= 512, no dbias) keeps the
     # first key block's dQ in an fp32 scratch when there is a second one
-    n_ws = ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal), dbias is not None)
+    drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
+    n_ws = 0 if drop[0] else ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal), dbias is not None)
     ws = torch.empty(n_ws, device=q.device, dtype=torch.float32) if n_ws else None
     path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
                                _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
-                               _stream(), *dbs, ld, _p(ws))
+                               _stream(), *dbs, ld, _p(ws), *drop)
     if path == 1:
         STATS["attention_bwd_onepass"] += 1
     if slab is not None:
@@ -457,6 +499,7 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
             if t is not None:
                 t.add_(slab[:rows[i], i * HD:(i + 1) * HD].sum(0))
     STATS["attention_bwd"] += 1
+    return path
 
 
 def gemm(a, b, trans_a=False, trans_b=False, bias=None, act="none", alpha=1.0, beta=0.0, out=None,

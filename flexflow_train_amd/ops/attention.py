@@ -21,6 +21,7 @@ from __future__ import annotations
 
 import math
 import os
+import warnings
 
 import torch
 
@@ -74,8 +75,8 @@ def _split_weights(W, E, Hl, kd, vd, Eq, Ek, Ev):
     return {"q": Wq, "k": Wk, "v": Wv, "o": Wo}
 
 
-def _torch_attention(q, k, v, causal, scale):
-    # q,k,v: [B, S, H, D] -> [B, S, H, D]
+def _torch_attention(q, k, v, causal, scale, drop=None):
+    # q,k,v: [B, S, H, D] -> [B, S, H, D]; drop = (keep mask [B, H, Sq, Sk], keep scale)
     qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
     s = torch.matmul(qt.float(), kt.float().transpose(-1, -2)) * scale
     if causal:
@@ -83,7 +84,101 @@ def _torch_attention(q, k, v, causal, scale):
         mask = torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1)
         s = s.masked_fill(mask, float("-inf"))
     p = torch.softmax(s, -1)
+    if drop is not None:
+        p = p * drop[0].to(p.dtype) * drop[1]
     return torch.matmul(p, vt.float()).transpose(1, 2).to(q.dtype)
+
+
+_M32 = 0xFFFFFFFF
+
+
+def _i64(x: int) -> int:
+    """A 64-bit pattern as the signed value torch's int64 holds."""
+    x &= (1 << 64) - 1
+    return x - (1 << 64) if x >> 63 else x
+
+
+def attention_dropout_mask(B, H, Sq, Sk, p, seed, device="cpu"):
+    """Keep mask of attention dropout: (bool [B, H, Sq, Sk], keep scale).
+
+    The definition that the flash kernels (csrc/kernels/attention.hip)
+    regenerate element by element; this is its second, independent
+    implementation, in torch integer ops on any device.  The decision for
+    probability (b, h, q, k) is a pure function of (seed, b, h, q, k, p):
+
+      key  = low 32 bits of splitmix64(seed, b * H + h):
+               z = seed + 0x9E3779B97F4A7C15 * (b * H + h + 1)   (mod 2^64)
+               z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+               z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+               z ^= z >> 31
+      x    = mix32((q * Sk + k) ^ key), 32-bit, logical shifts:
+               x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+      keep iff (x >> 8) >= T,   T = round(p * 2^24)
+
+    Kept probabilities are scaled by 2^24 / (2^24 - T), exactly unbiased for
+    the realised drop rate T / 2^24.  ``seed`` is the effective seed (host
+    seed plus the device step word, mod 2^64): an int, or a 1-element int64
+    tensor (read without a host synchronisation).  Needs Sq * Sk < 2^32 and
+    p < 1; p <= 0 keeps everything.
+    """
+    T = K.attention_dropout_threshold(p)
+    if Sq * Sk >= 1 << 32:
+        raise ValueError(f"attention: dropout needs Sq * Sk < 2^32, got {Sq} x {Sk}")
+    device = torch.device(device)
+    if T == 0:
+        return torch.ones(B, H, Sq, Sk, dtype=torch.bool, device=device), 1.0
+    i64 = dict(dtype=torch.int64, device=device)
+    if isinstance(seed, torch.Tensor):
+        s = seed.reshape(1).to(**i64)
+    else:
+        s = torch.tensor([_i64(int(seed))], **i64)
+
+    def lsr(z, n):  # logical shift right of a 64-bit pattern held in int64
+        return (z >> n) & ((1 << (64 - n)) - 1)
+
+    # int64 add / multiply wrap mod 2^64, which is the arithmetic wanted
+    z = s + torch.arange(1, B * H + 1, **i64) * _i64(0x9E3779B97F4A7C15)
+    z = (z ^ lsr(z, 30)) * _i64(0xBF58476D1CE4E5B9)
+    z = (z ^ lsr(z, 27)) * _i64(0x94D049BB133111EB)
+    z = z ^ lsr(z, 31)
+    key = (z & _M32).view(B, H, 1, 1)
+    idx = (torch.arange(Sq, **i64).view(Sq, 1) * Sk + torch.arange(Sk, **i64).view(1, Sk)).view(1, 1, Sq, Sk)
+    x = idx ^ key                     # values stay in [0, 2^32): >> is logical
+    x = x ^ (x >> 16)
+    x = (x * 0x7FEB352D) & _M32       # < 2^63: no wrap
+    x = x ^ (x >> 15)
+    x = (x * 0x846CA68B) & _M32       # may wrap mod 2^64: the low 32 bits are unaffected
+    x = x ^ (x >> 16)
+    return (x >> 8) >= T, float(1 << 24) / float((1 << 24) - T)
+
+
+def _drop_seed(ctx: OpContext) -> int:
+    """Host part of the attention-dropout seed (ctx.seed is per operator and rank)."""
+    return (int(ctx.seed) * 7919 + 0x5DEECE66D) & ((1 << 63) - 1)
+
+
+def _drop_step(ctx: OpContext, device) -> torch.Tensor:
+    """Advance the operator's device-resident forward counter and return a
+    private copy of its new value: the step word of this forward's mask, kept
+    for its backward.  Both are device operations, so a captured forward
+    draws a fresh mask on every replay, and the sequence of masks depends only
+    on the number of training forwards run."""
+    cnt = ctx.extra.get("attn_drop_counter")
+    if cnt is None or cnt.device != device:
+        if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            # created inside a capture, the counter's zero fill would be replayed too
+            raise RuntimeError("attention dropout: run one eager training forward before graph capture")
+        cnt = ctx.extra["attn_drop_counter"] = torch.zeros(1, dtype=torch.int64, device=device)
+    cnt.add_(1)
+    return cnt.clone()
+
+
+def _fallback_mask(drop, B, H, Sq, Sk):
+    """(keep mask, keep scale) of the torch fallback from a forward's drop record."""
+    if drop is None:
+        return None
+    p, seed, step = drop
+    return attention_dropout_mask(B, H, Sq, Sk, p, step + _i64(seed), step.device)
 
 
 def _layout_dims(attrs: dict, Hl: int):
@@ -205,22 +300,34 @@ class MultiHeadAttentionOp(OpImpl):
             proj = (q, k, v)
         grp = ctx.extra.get("seq_group")
         use_flash = (q.is_cuda and q.dtype == torch.bfloat16 and kd == vd and kd in (64, 128) and K.available())
+        # dropout on the attention probabilities: training only.  drop = (p,
+        # host seed, this forward's copy of the device step word), saved for
+        # the backward; the mask is attention_dropout_mask(seed + step word)
+        p_drop = float(ctx.a("dropout", 0.0) or 0.0) if ctx.training else 0.0
+        drop = None
         if grp is not None and grp.size > 1:
+            if p_drop > 0 and not ctx.extra.get("attn_drop_warned"):
+                ctx.extra["attn_drop_warned"] = True
+                warnings.warn(f"{ctx.name}: attention dropout is not applied on the sequence-parallel path")
             # sequence-sharded q/k/v: Ulysses all-to-all or ring attention
             o, lse = SP.sp_attention_fwd(q, k, v, causal, scale, grp, SP.choose_mode(ctx.attrs, Hl, grp))
             lse = ("sp", lse)
-        elif use_flash:
-            o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale)
         else:
-            o, lse = _torch_attention(q, k, v, causal, scale), None
+            if p_drop > 0 and K.attention_dropout_threshold(p_drop):
+                drop = (p_drop, _drop_seed(ctx), _drop_step(ctx, q.device))
+            if use_flash:
+                kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+                o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale, **kw)
+            else:
+                o, lse = _torch_attention(q, k, v, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk)), None
         o2 = o.reshape(B * Sq, Hl * vd)
         out = matmul(o2, ws["o"], bias=b_out)
         saved = (x2, k_in if not self_attn else None, v_in if not self_attn else None, proj, o, lse, ws,
-                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale))
+                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale), drop)
         return [out.view(B, Sq, E)], saved
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
-        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims = saved
+        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims, drop = saved
         B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale = dims
         dW = weight_grads[0]
         db_in = weight_grads[1] if len(weight_grads) > 1 else None
@@ -271,12 +378,13 @@ class MultiHeadAttentionOp(OpImpl):
                 dbf = db_in.reshape(-1)
                 n = Hl * kd
                 fused_db = (dbf[:n], dbf[n:2 * n], dbf[2 * n:3 * n])
-            K.attention_bwd(q, k, v, o, lse, do4, dq, dk, dv, causal=causal, scale=scale, dbias=fused_db)
+            kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+            K.attention_bwd(q, k, v, o, lse, do4, dq, dk, dv, causal=causal, scale=scale, dbias=fused_db, **kw)
             if fused_db is not None:
                 db_in = None   # accumulated by the attention backward kernels
         else:
             qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-            ref = _torch_attention(qf, kf, vf, causal, scale)
+            ref = _torch_attention(qf, kf, vf, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk))
             ref.float().backward(do4.float())
             dq, dk, dv = (t.grad.to(do.dtype) for t in (qf, kf, vf))
             if self_attn:

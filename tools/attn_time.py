@@ -5,6 +5,7 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
 
     python tools/attn_time.py [iters]
     python tools/attn_time.py --pipe-ab | --delta-ab | --onepass-ab   (same-process A/B of a kernel switch)
+    python tools/attn_time.py --dropout 0.1                           (attention dropout against p = 0)
 """
 import json
 import os
@@ -88,7 +89,42 @@ def pmc_run(n=5):
         print(name, "done", flush=True)
 
 
+def dropout_ab(p, iters, rounds=5):
+    """Interleaved same-process timing of the forward and the backward with
+    attention dropout `p` against p = 0.  With p > 0 the backward is the
+    dQ + dK/dV kernel pair at every shape (the one-pass kernel of the BERT
+    shapes has no dropout form)."""
+    import statistics
+    for name, (B, S, H, D, causal) in SHAPES.items():
+        g = torch.Generator(device="cuda").manual_seed(0)
+        qkv = torch.randn(B, S, 3, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+        do = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        dqkv = torch.empty_like(qkv)
+        t = {}
+        for _ in range(rounds):
+            for pp in (0.0, p):
+                kw = dict(causal=causal, dropout_p=pp, seed=1234)
+                o, lse = K.attention_fwd(q, k, v, **kw)
+                t.setdefault(("fwd", pp), []).append(_time(lambda: K.attention_fwd(q, k, v, out=o, **kw), iters))
+                t.setdefault(("bwd", pp), []).append(_time(
+                    lambda: K.attention_bwd(q, k, v, o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], **kw),
+                    iters))
+        fl = 4 * B * H * S * S * D * (0.5 if causal else 1.0)
+        med = {key: statistics.median(v) for key, v in t.items()}
+        rec = {"shape": name, "dropout": p}
+        for which, mul in (("fwd", 1.0), ("bwd", 2.5)):
+            for pp, tag in ((0.0, "p0"), (p, "drop")):
+                rec[f"{which}_ms_{tag}"] = round(med[(which, pp)], 4)
+                rec[f"{which}_tflops_{tag}"] = round(mul * fl / med[(which, pp)] / 1e9, 1)
+            rec[f"{which}_rounds_p0"] = [round(x, 4) for x in t[(which, 0.0)]]
+            rec[f"{which}_rounds_drop"] = [round(x, 4) for x in t[(which, p)]]
+        print(json.dumps(rec), flush=True)
+
+
 def main():
+    if "--dropout" in sys.argv:        # attention dropout against p = 0, forward and backward
+        return dropout_ab(float(sys.argv[sys.argv.index("--dropout") + 1]), 30)
     if "--pmc-run" in sys.argv:
         return pmc_run()
     if "--pipe-ab" in sys.argv:        # software-pipelined forward

@@ -58,7 +58,8 @@ def summarise(lines, st, end):
                  if i > h and "branch" in l and labels.get(l.split()[-1], i) <= h), (None, None))
     loop = ins(body[s:e + 1]) if e else []
     post = ins(body[e + 1:]) if e else []
-    return {"loop": len(loop), "loop_mix": collections.Counter(loop).most_common(12), "post": len(post),
+    return {"loop": len(loop), "loop_scratch": sum(i.startswith("scratch_") for i in loop),
+            "loop_mix": collections.Counter(loop).most_common(12), "post": len(post),
             "post_mix": collections.Counter(post).most_common(16)}
 
 
