@@ -1026,6 +1026,9 @@ LocalTrainingBacking::LocalTrainingBacking(const ComputationGraph& cg, LocalOpti
       continue;
     }
     if (!reg.count(t)) throw FFError("local execution: no CPU implementation for " + to_string(t));
+    if (t == OpType::MULTIHEAD_ATTENTION && cg_.layer_data_inputs(n).size() != 3)
+      throw FFError("local execution: attention key lengths (the fourth input of " + node.label.name +
+                    ") are not supported");
     bool ng = false;
     for (auto const& v : node.inputs) ng = ng || needs_grad_[v];
     for (size_t i = 0; i < node.outputs.size(); ++i) needs_grad_[{n, static_cast<int>(i)}] = ng;

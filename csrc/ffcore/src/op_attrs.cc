@@ -139,6 +139,7 @@ using ParFn = std::function<PShapes(const OpAttrs&, const PShapes&)>;
 
 struct OpSpec {
   int num_inputs = 1;  // -1 variadic
+  std::function<int(const OpAttrs&)> arity;  // optional: the input count depends on the attributes
   std::map<std::string, AttrValue> defaults;
   std::vector<std::string> required;
   std::function<std::vector<std::string>(const OpAttrs&)> weights;
@@ -575,9 +576,17 @@ OpSpec embedding_spec() {
 // Weight: [qSize*kdim + kSize*kdim + vSize*vdim + vdim*embed_dim, num_heads]
 // (ops/attention.cc:136-170); input bias [2*kdim + vdim, num_heads],
 // output bias [embed_dim].
+// With the attribute key_lengths = true the node has a fourth input, the
+// per-sample key lengths: rank 1 [batch], an integer dtype.  Keys at or past a
+// sample's length do not exist for that sample.  The attribute is absent from
+// a 3-input node (no default), so graphs without lengths serialise as before.
+bool mha_has_lengths(const OpAttrs& a) { return a.has("key_lengths") && a.b("key_lengths"); }
+bool is_integer_dtype(DataType t) { return t == DataType::INT32 || t == DataType::INT64; }
+
 OpSpec mha_spec() {
   OpSpec s;
   s.num_inputs = 3;
+  s.arity = [](const OpAttrs& a) { return mha_has_lengths(a) ? 4 : 3; };
   s.required = {"embed_dim", "num_heads"};
   s.defaults = {{"kdim", int64_t(0)}, {"vdim", int64_t(0)}, {"dropout", 0.0}, {"bias", true},
                 {"add_bias_kv", false}, {"add_zero_attn", false}, {"causal", false},
@@ -597,7 +606,12 @@ OpSpec mha_spec() {
     return a.i("vdim") > 0 ? a.i("vdim") : a.i("embed_dim") / a.i("num_heads");
   };
   s.out = [](const OpAttrs& a, const Shapes& in) {
-    for (auto const& t : in) require(nd(t) == 3, a, "q/k/v must be [batch, seq, feature]");
+    for (int i = 0; i < 3; ++i) require(nd(in[i]) == 3, a, "q/k/v must be [batch, seq, feature]");
+    if (in.size() > 3) {
+      require(nd(in[3]) == 1, a, "key lengths must be rank 1 [batch]");
+      require(is_integer_dtype(in[3].dtype), a, "key lengths must have an integer dtype");
+      require(in[3].dims[0] == in[0].dims[0], a, "key lengths batch mismatch");
+    }
     require(in[0].dims[0] == in[1].dims[0] && in[0].dims[0] == in[2].dims[0], a, "batch mismatch");
     require(in[1].dims[1] == in[2].dims[1], a, "key/value sequence length mismatch");
     return Shapes{TensorShape{{in[0].dims[0], in[0].dims[1], a.i("embed_dim")}, in[0].dtype}};
@@ -613,10 +627,22 @@ OpSpec mha_spec() {
     return w;
   };
   auto parse = [](const OpAttrs& a, const PShapes& in) {
-    for (auto const& t : in) {
+    for (int i = 0; i < 3; ++i) {
+      auto const& t = in[i];
       require(t.num_dims() == 3, a, "q/k/v must be rank 3");
       require(t.sum_degree == 1, a, "attention inputs cannot be partial sums");
       require(t.dim(2).degree == 1, a, "feature dim must be unpartitioned");
+    }
+    if (in.size() > 3) {
+      auto const& l = in[3];
+      require(l.num_dims() == 1, a, "key lengths must be rank 1 [batch]");
+      require(is_integer_dtype(l.dtype), a, "key lengths must have an integer dtype");
+      require(l.sum_degree == 1, a, "key lengths cannot be a partial sum");
+      require(l.dim(0).degree == in[0].dim(0).degree, a, "key lengths batch degree differs from q");
+      require(l.discard_copy_degree == in[0].discard_copy_degree, a, "key lengths replica degree differs from q");
+      // ring / Ulysses attention has no per-sample lengths
+      require(in[0].dim(1).degree == 1 && in[1].dim(1).degree == 1 && in[2].dim(1).degree == 1, a,
+              "key lengths need an unpartitioned sequence dim");
     }
     require(in[0].dim(0).degree == in[1].dim(0).degree && in[0].dim(0).degree == in[2].dim(0).degree,
             a, "q/k/v batch degrees differ");
@@ -1385,11 +1411,14 @@ OpAttrs normalize_attrs(OpAttrs attrs) {
 }
 
 int num_weights(const OpAttrs& a) { return static_cast<int>(spec_of(a).weights(a).size()); }
-int num_data_inputs(const OpAttrs& a) { return spec_of(a).num_inputs; }
+int num_data_inputs(const OpAttrs& a) {
+  auto const& sp = spec_of(a);
+  return sp.arity ? sp.arity(a) : sp.num_inputs;
+}
 std::vector<std::string> weight_names(const OpAttrs& a) { return spec_of(a).weights(a); }
 
 static void check_arity(const OpAttrs& a, size_t n) {
-  int k = spec_of(a).num_inputs;
+  int k = num_data_inputs(a);
   if (k >= 0 && static_cast<size_t>(k) != n)
     throw FFError(to_string(a.type) + ": expected " + std::to_string(k) + " inputs, got " + std::to_string(n));
 }

@@ -129,6 +129,11 @@ std::optional<std::vector<ParallelTensorShape>> required_input_shapes(const Comp
     auto p = batch_seq_shape(s, ref, cfg.batch, cfg.seq);
     ps.push_back(p);
   }
+  // the key lengths of attention ([batch], rank 1) follow q's batch degree;
+  // batch_seq_shape leaves inputs of another rank than input 0 whole
+  if (op.type == OpType::MULTIHEAD_ATTENTION && ss.size() == 4 && cfg.batch > 1 && ss[3].num_dims() == 1 &&
+      ss[3].dims[0] == ref.dims[0] && ss[3].dims[0] % cfg.batch == 0)
+    ps[3] = lift_to_parallel_with_degrees(ss[3], 1, 1, {cfg.batch});
   // every requested degree must actually apply to input 0
   if (cfg.batch > 1 && (ref.num_dims() < 1 || ps[0].dim(0).degree != cfg.batch)) return std::nullopt;
   if (cfg.seq > 1 && (ref.num_dims() < 3 || ps[0].dim(attribute_dim(ref)).degree != cfg.seq)) return std::nullopt;

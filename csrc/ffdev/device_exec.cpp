@@ -751,6 +751,7 @@ std::string unsupported(const ComputationGraph& cg, int n) {
   }
   if (t == OpType::MULTIHEAD_ATTENTION) {
     const auto ins = cg.layer_data_inputs(n);
+    if (ins.size() == 4) return "attention key lengths (the fourth input of " + node.label.name + ")";
     if (ins.size() != 3 || cg.shape(ins[0]).dims.size() != 3) return "attention inputs";
     return "";
   }

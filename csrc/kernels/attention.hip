@@ -50,6 +50,21 @@
 // probabilities (the LSE is that of a p = 0 call); O = rs (keep . P) V, so
 // delta = rowsum(dO * O) is unchanged and dS = P (keep rs dP - delta),
 // dV = rs (keep . P)^T dO.
+//
+// Per-sample key lengths (VARLEN instantiations of the forward, dQ and dK/dV
+// kernels; AttnTensors::kv_lens, int32 [B] on the device).  Keys >=
+// kv_lens[b] do not exist for sample b: every bound on the key axis (tile
+// count, tile loads, masks, the dK/dV wave's key test) takes the sample's
+// length, read once per workgroup as a scalar and clamped to [0, Sk], in the
+// place of Sk.  Rows past the length are never read (the loaders return
+// zeros, as they do past Sk), the forward and dQ kernels stop at the last
+// live key tile, a dK/dV workgroup whose key block is wholly dead skips its
+// query loop, and dK = dV = 0 is stored for every dead key below the physical
+// Sk (the gradient buffers are uninitialised).  A row without a live key gets
+// o = 0, lse = -inf and dQ = 0.  The dropout hash index and the dbias slab
+// rows keep the physical Sk.  The backward with lengths is the dQ + dK/dV
+// pair; a call without lengths runs the VARLEN = false kernels, in which the
+// bound is P.Sk as before.
 #include <cstdlib>
 
 #include "kernels.h"
@@ -83,7 +98,20 @@ struct AttnParams {
   float drop_rs;            // keep scale 2^24 / (2^24 - T)
   uint64_t seed;
   const int64_t* seed_dev;  // optional device-resident addend of the seed
+  // per-sample key lengths (VARLEN kernels only; appended like the dropout fields)
+  const int32_t* kv_lens;   // [B]; keys >= kv_lens[b] of sample b do not exist
 };
+
+// Key-axis bound of sample b.  VARLEN: the sample's own length, read from the
+// device (so a captured launch follows the tensor) and clamped to [0, Sk] so
+// that a bad value cannot read out of bounds; b is uniform over the
+// workgroup, which makes this one scalar load.  Otherwise the physical Sk.
+// The dropout hash index keeps the physical Sk as its row stride either way.
+template <bool VARLEN>
+__device__ __forceinline__ int key_len(const AttnParams& P, int b) {
+  if constexpr (VARLEN) return __builtin_amdgcn_readfirstlane(min(max(P.kv_lens[b], 0), P.Sk));
+  else return P.Sk;
+}
 
 // Dropout hash (definition in the header comment).  drop_key is uniform over
 // the workgroup: made a scalar so the per-element xor takes it from an SGPR.
@@ -263,7 +291,7 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 // DROP: the dropped probabilities are zeroed after the row sum is taken, so
 // m, l and the LSE are those of the undropped softmax; the keep scale is
 // folded into the epilogue's 1 / l.
-template <int D, bool CAUSAL, bool DROP = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   constexpr int KS = D / 16;        // k-steps over the head dim
   constexpr int DT = D / 32;        // 32-wide output tiles over the head dim
@@ -282,6 +310,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   const int qw = q_blk + wave * 32;
   const int q = qw + (lane & 31);
   const bool q_ok = q < P.Sq;
+  const int Skl = key_len<VARLEN>(P, b);  // keys of this sample
 
   // Q as the B operand of S^T = K Q^T: lane holds Q[q][16ks + 8h .. +8]
   bf16x8 qf[KS];
@@ -302,12 +331,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
     drow = static_cast<unsigned>(q) * static_cast<unsigned>(P.Sk) + 4u * h;
   }
 
-  int n_tiles = (P.Sk + KV - 1) / KV;
+  int n_tiles = (Skl + KV - 1) / KV;
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, b, hh, 0, P.Sk);
-  vl.load(P.v, b, hh, 0, P.Sk);
+  kl.load(P.k, b, hh, 0, Skl);
+  vl.load(P.v, b, hh, 0, Skl);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -318,8 +347,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
     if (has_next) {  // issue next tile's HBM loads before this tile's MFMAs
-      kl.load(P.k, b, hh, k0 + KV, P.Sk);
-      vl.load(P.v, b, hh, k0 + KV, P.Sk);
+      kl.load(P.k, b, hh, k0 + KV, Skl);
+      vl.load(P.v, b, hh, k0 + KV, Skl);
     }
     const bool wave_active = !CAUSAL || (k0 <= qw + 31);
     if (wave_active) {
@@ -339,14 +368,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
       // ---- mask (only tiles that cross the sequence end or the causal
       // diagonal — a wave-uniform branch), tile max of the RAW scores: the
       // softmax scale is folded into one FMA per score inside exp2 below
-      const bool need_mask = (k0 + KV > P.Sk) || (CAUSAL && k0 + KV - 1 > qw);
+      const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw);
       if (need_mask) {
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (key >= P.Sk || (CAUSAL && key > q)) s[kt][r] = -INFINITY;
+            if (key >= Skl || (CAUSAL && key > q)) s[kt][r] = -INFINITY;
           }
       }
       // two independent v_max3 chains over the 32 scores (16 issues)
@@ -631,10 +660,23 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(AttnParams P) {
 // this one — the separate delta pass (a full re-read of dO and O) goes away.
 // DROP: dS^T = P^T (keep rs dP^T - delta); same (lane -> query, register ->
 // key) coordinates as the forward.
-template <int D, bool CAUSAL, bool FUSED_DELTA = false, bool DROP = false>
+// VARLEN with DROP (XDELTA): delta is taken from the probabilities, delta =
+// sum_k P (keep rs dP), not left at dlt = rowsum(dO * O).  The two are equal
+// in exact arithmetic, but O is stored in bf16 and with dropout it is rounded
+// even where a row has one key (O = rs V[0]); that row's dS is exactly zero,
+// and with dlt the rounding of O came out as dS instead (a sample of length 1
+// put the dQ / dK error of a batch at 6e-3 to 1.1e-2 against 2.4e-3 without
+// it).  Lengths make rows of few keys the normal case, so these forms pay for
+// it: the loop runs on dlt as before, also sums P (keep rs dP) per lane and
+// accumulates bq^T = K^T P^T from the K^T fragments of the dQ product (one
+// more MFMA product, DT more accumulators), and the epilogue adds
+// (dlt - delta) bq^T to dQ^T and writes delta for the dK / dV kernel.
+template <int D, bool CAUSAL, bool FUSED_DELTA = false, bool DROP = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, KV = 64;
   constexpr int TILE_BYTES = KV * D * 2;
+  constexpr bool XDELTA = VARLEN && DROP;  // delta from the probabilities (comment above)
+  static_assert(!XDELTA || FUSED_DELTA, "the exact delta is written for the dK / dV kernel that follows");
   __shared__ __attribute__((aligned(16))) unsigned char smem[4 * TILE_BYTES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
   int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;   // causal: longest-first (fwd)
@@ -644,6 +686,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   const int qw = q_blk + wave * 32;
   const int q = qw + (lane & 31);
   const bool q_ok = q < P.Sq;
+  const int Skl = key_len<VARLEN>(P, b);  // keys of this sample
 
   bf16x8 qf[KS], df[KS];
 #pragma unroll
@@ -672,7 +715,8 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
       }
     }
     dlt = part + __shfl_xor(part, 32, 64);
-    if (q_ok && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = dlt;
+    if constexpr (!XDELTA)  // XDELTA writes the exact delta after the loop
+      if (q_ok && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = dlt;
   } else {
     dlt = q_ok ? P.delta[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
   }
@@ -680,6 +724,13 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   f32x16 dq[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) dq[dt] = f32x16{};
+  // XDELTA: bq^T = K^T P^T next to dQ^T, and this lane's share of sum_k P (keep rs dP)
+  [[maybe_unused]] f32x16 bq[XDELTA ? DT : 1];
+  [[maybe_unused]] float dsum = 0.f;
+  if constexpr (XDELTA) {
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) bq[dt] = f32x16{};
+  }
   [[maybe_unused]] unsigned dkey = 0, drow = 0;
   if constexpr (DROP) {
     dkey = drop_key(P, bh);
@@ -695,12 +746,12 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     }
   };
 
-  int n_tiles = (P.Sk + KV - 1) / KV;
+  int n_tiles = (Skl + KV - 1) / KV;
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, b, hh, 0, P.Sk);
-  vl.load(P.v, b, hh, 0, P.Sk);
+  kl.load(P.k, b, hh, 0, Skl);
+  vl.load(P.v, b, hh, 0, Skl);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -711,15 +762,16 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
     if (has_next) {
-      kl.load(P.k, b, hh, k0 + KV, P.Sk);
-      vl.load(P.v, b, hh, k0 + KV, P.Sk);
+      kl.load(P.k, b, hh, k0 + KV, Skl);
+      vl.load(P.v, b, hh, k0 + KV, Skl);
     }
     const bool wave_active = !CAUSAL || (k0 <= qw + 31);
-    const bool need_mask = (k0 + KV > P.Sk) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= P.Sq);
+    const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= P.Sq);
     if (wave_active) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         f32x16 s = f32x16{}, dp = f32x16{};
+        [[maybe_unused]] bf16x8 pf[2];  // P^T as the two operand fragments (XDELTA)
         prio_hi(P);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -733,8 +785,23 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             float pv = fexp2(s[r] * P.scale_log2 - lse);
-            if (key >= P.Sk || (CAUSAL && key > q) || !q_ok) pv = 0.f;
-            s[r] = pv * (kept(dp[r], k0, kt, r) - dlt);  // dS^T
+            if (key >= Skl || (CAUSAL && key > q) || !q_ok) pv = 0.f;
+            if constexpr (XDELTA) {
+              const float kd = kept(dp[r], k0, kt, r);
+              pf[r >> 3][r & 7] = f2bf(pv);
+              dsum = fmaf(pv, kd, dsum);
+              s[r] = pv * (kd - dlt);
+            } else {
+              s[r] = pv * (kept(dp[r], k0, kt, r) - dlt);  // dS^T
+            }
+          }
+        } else if constexpr (XDELTA) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float pv = fexp2(s[r] * P.scale_log2 - lse), kd = kept(dp[r], k0, kt, r);
+            pf[r >> 3][r & 7] = f2bf(pv);
+            dsum = fmaf(pv, kd, dsum);
+            s[r] = pv * (kd - dlt);
           }
         } else {
 #pragma unroll
@@ -744,8 +811,17 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
           bf16x8 sf = acc_to_frag(s, st);
+          if constexpr (XDELTA) {
 #pragma unroll
-          for (int dt = 0; dt < DT; ++dt) dq[dt] = mfma32(tr_frag<D>(Kt, kt * 32 + 16 * st, dt, lane), sf, dq[dt]);
+            for (int dt = 0; dt < DT; ++dt) {
+              const bf16x8 ktf = tr_frag<D>(Kt, kt * 32 + 16 * st, dt, lane);
+              dq[dt] = mfma32(ktf, sf, dq[dt]);
+              bq[dt] = mfma32(ktf, pf[st], bq[dt]);
+            }
+          } else {
+#pragma unroll
+            for (int dt = 0; dt < DT; ++dt) dq[dt] = mfma32(tr_frag<D>(Kt, kt * 32 + 16 * st, dt, lane), sf, dq[dt]);
+          }
         }
         prio_lo(P);
       }
@@ -756,6 +832,17 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
       vl.store(nxt + TILE_BYTES);
     }
     __syncthreads();
+  }
+  if constexpr (XDELTA) {
+    // dS = P (kdP - delta) = P (kdP - dlt) + P (dlt - delta): the loop used
+    // dlt, the rest is one rank-1 update of dQ^T by bq^T, the query on the lane
+    const float delta = dsum + __shfl_xor(dsum, 32, 64);
+    const float c = dlt - delta;
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) dq[dt][r] = fmaf(c, bq[dt][r], dq[dt][r]);
+    if (q_ok && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = delta;
   }
   if (P.dbq && P.db_ld) {
     if (qw < P.Sq)  // waves wholly past the sequence own no slab row
@@ -791,10 +878,11 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
 // registers, so the hash index q * Sk + key steps by Sk per register; the dP
 // accumulator starts from zero and -delta is added after the keep scale
 // (dS = P (keep rs dP - delta)); dV takes keep . P and rs at the store.
-template <int D, bool CAUSAL, int NKT, bool PF = false, bool DROP = false>
+template <int D, bool CAUSAL, int NKT, bool PF = false, bool DROP = false, bool VARLEN = false>
 __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
   static_assert(!PF || NKT == 1, "PF prefetch is written for one key subtile per wave");
   static_assert(!DROP || NKT == 1, "dropout is written for one key subtile per wave");
+  static_assert(!VARLEN || NKT == 1, "key lengths are written for one key subtile per wave");
   constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32 * NKT;
   constexpr int TILE_BYTES = QT * D * 2;
   constexpr int STAGE = 2 * TILE_BYTES + 2 * QT * 4;  // Q, dO, lse, delta
@@ -806,15 +894,27 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
   const int b = bh / P.H, hh = bh % P.H;
   const int k_blk = kb * (4 * KW);
   const int kw = k_blk + wave * KW;
+  // keys of this sample.  Without lengths every use reads P.Sk in place, as
+  // it did before the kernel had lengths: held in a local, the causal forms
+  // compiled to another instruction stream (3294 against 3305 instructions at
+  // D = 64), and a call without lengths is to run the code it ran before
+  [[maybe_unused]] int len_v = 0;
+  if constexpr (VARLEN) len_v = key_len<true>(P, b);
+  auto Skl = [&]() -> int {
+    if constexpr (VARLEN) return len_v;
+    else return P.Sk;
+  };
 
   // K, V rows as B operands (lane holds row `key`, d = 16ks + 8h ..)
   bf16x8 kf[NKT][KS], vf[NKT][KS];
   int key[NKT];
-  bool k_ok[NKT];
+  bool k_ok[NKT];  // the key exists (VARLEN: below the sample's length)
+  bool k_st[NKT];  // the key has a dK / dV row to write (below the physical Sk)
 #pragma unroll
   for (int j = 0; j < NKT; ++j) {
     key[j] = kw + 32 * j + (lane & 31);
-    k_ok[j] = key[j] < P.Sk;
+    k_ok[j] = key[j] < Skl();
+    k_st[j] = VARLEN ? key[j] < P.Sk : k_ok[j];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
       kf[j][ks] = k_ok[j] ? *reinterpret_cast<const bf16x8*>(P.k.p + b * P.k.sb +
@@ -833,7 +933,9 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt) dk[j][dt] = dv[j][dt] = f32x16{};
 
-  const int n_q_tiles = (P.Sq + QT - 1) / QT;
+  // VARLEN: a key block wholly past the length skips the query loop and
+  // stores zeros (dK = dV = 0, and zero partials into the dbias slab)
+  const int n_q_tiles = (VARLEN && k_blk >= Skl()) ? 0 : (P.Sq + QT - 1) / QT;
   const int t0 = CAUSAL ? (k_blk / QT) : 0;
   // dropout: hash index of register r of a subtile = (first query + 4 h +
   // (r & 3) + 8 (r >> 2)) * Sk + key
@@ -900,7 +1002,7 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
       fetch_scalars(q0 + QT);
     }
     const bool wave_active = !CAUSAL || (q0 + QT - 1 >= kw);
-    const bool need_mask = (q0 + QT > P.Sq) || (CAUSAL && q0 < kw + KW - 1) || (kw + KW - 1 >= P.Sk);
+    const bool need_mask = (q0 + QT > P.Sq) || (CAUSAL && q0 < kw + KW - 1) || (kw + KW - 1 >= Skl());
     if (wave_active) {
       // DROP at D = 128 (all 512 registers in use): the fragment offsets of
       // the per-pair reads are derived from the lane id again in every tile.
@@ -1051,12 +1153,12 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
   for (int j = 0; j < NKT; ++j) {
     bf16* krow = P.dk + b * P.dk_sb + static_cast<int64_t>(key[j]) * P.dk_ss + hh * P.dk_sh;
     bf16* vrow = P.dv + b * P.dv_sb + static_cast<int64_t>(key[j]) * P.dv_ss + hh * P.dv_sh;
-    if (P.wide_store) {   // every lane swaps; k_ok guards the stores
-      store_rows16<DT>(krow, dk[j], P.scale, h, k_ok[j]);
-      store_rows16<DT>(vrow, dv[j], vmul, h, k_ok[j]);
+    if (P.wide_store) {   // every lane swaps; k_st guards the stores
+      store_rows16<DT>(krow, dk[j], P.scale, h, k_st[j]);
+      store_rows16<DT>(vrow, dv[j], vmul, h, k_st[j]);
       continue;
     }
-    if (!k_ok[j]) continue;
+    if (!k_st[j]) continue;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -1400,6 +1502,7 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
     P.seed = t.seed;
     P.seed_dev = t.seed_dev;
   }
+  P.kv_lens = t.kv_lens;
   return P;
 }
 
@@ -1415,6 +1518,23 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
   // in-wave overlap gains
   const char* pe = getenv("FFK_ATTN_FWD_PIPE");
   const int pipe = pe ? atoi(pe) : 0;
+  if (P.kv_lens) {  // key lengths: the default variant only, like dropout
+#define FFK_ATTN_FWD_VL(DD, CC)                                                                  \
+  if (P.drop_thr) hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, true, true>), grid, block, 0, st, P); \
+  else hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, false, true>), grid, block, 0, st, P)
+    if (D == 64) {
+      if (causal) { FFK_ATTN_FWD_VL(64, true); }
+      else { FFK_ATTN_FWD_VL(64, false); }
+    } else if (D == 128) {
+      if (causal) { FFK_ATTN_FWD_VL(128, true); }
+      else { FFK_ATTN_FWD_VL(128, false); }
+    } else {
+      throw std::invalid_argument("attention: head dim must be 64 or 128");
+    }
+#undef FFK_ATTN_FWD_VL
+    FFK_LAUNCH_CHECK("attention_fwd");
+    return;
+  }
   if (P.drop_thr) {  // dropout: the default variant only, whatever the experimental switches say
     if (D == 64) {
       if (causal) hipLaunchKernelGGL((attn_fwd_kernel<64, true, true>), grid, block, 0, st, P);
@@ -1446,9 +1566,9 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
   FFK_LAUNCH_CHECK("attention_fwd");
 }
 
-template <int D, bool CAUSAL, bool DROP = false>
+template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
 static void launch_dkdv(int nkt, dim3 grid, dim3 block, hipStream_t st, const AttnParams& P) {
-  if constexpr (D == 64 && !DROP) {
+  if constexpr (D == 64 && !DROP && !VARLEN) {
     if (nkt == 2) {
       hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 2>), grid, block, 0, st, P);
       return;
@@ -1465,25 +1585,25 @@ static void launch_dkdv(int nkt, dim3 grid, dim3 block, hipStream_t st, const At
   // of scratch, reloaded in the loop), which takes the per-pair reads
   if constexpr (!DROP) {
     if (pf && D == 64) {
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, D == 64>), grid, block, 0, st, P);
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, D == 64, false, VARLEN>), grid, block, 0, st, P);
       return;
     }
   }
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, false, DROP>), grid, block, 0, st, P);
+  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, false, DROP, VARLEN>), grid, block, 0, st, P);
 }
 
 // The one-pass kernel's shapes; both switches are read per call (the A/B tool
 // and the tests flip them inside one process).  FFK_ATTN_BWD_FUSED_DELTA=0
 // asks for the three-launch path and so also rules the one-pass kernel out.
-static bool onepass_eligible(int Sk, int D, bool causal, bool dbias, bool drop = false) {
-  if (D != 64 || causal || Sk > 512 || dbias || drop) return false;
+static bool onepass_eligible(int Sk, int D, bool causal, bool dbias, bool drop = false, bool varlen = false) {
+  if (D != 64 || causal || Sk > 512 || dbias || drop || varlen) return false;
   const char* oe = getenv("FFK_ATTN_BWD_ONEPASS");
   const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
   return (oe ? atoi(oe) != 0 : true) && (fde ? atoi(fde) != 0 : true);
 }
 
-int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias) {
-  if (!onepass_eligible(Sk, D, causal, dbias) || Sk <= 256) return 0;
+int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias, bool varlen) {
+  if (!onepass_eligible(Sk, D, causal, dbias, false, varlen) || Sk <= 256) return 0;
   return static_cast<int64_t>(B) * H * ((Sq + 63) / 64) * 64 * 64;
 }
 
@@ -1492,7 +1612,8 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
   // a second key block needs the workspace: callers that pass none keep the
   // two-kernel path
-  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv, P.drop_thr != 0) && (Sk <= 256 || ws)) {
+  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv, P.drop_thr != 0, P.kv_lens != nullptr) &&
+      (Sk <= 256 || ws)) {
     hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(static_cast<unsigned>(B * H)), dim3(512), 0, st, P, ws);
     FFK_LAUNCH_CHECK("attention_bwd");
     return 1;
@@ -1507,8 +1628,9 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   // NKT = 2 (64 keys per wave) halves LDS reads per MFMA but needs ~500
   // registers (1 wave/SIMD, spills when causal): measured 0.24 vs 0.21 ms
   // (BERT shape) and 0.92 vs 0.56 ms (GPT causal) — opt-in only.
-  // (dropout: the default variants only, NKT = 1 and the fused delta)
-  const int nkt = D == 64 && nkt_env == 2 && !P.drop_thr ? 2 : 1;
+  // (dropout and key lengths: the default variants only, NKT = 1 and the
+  // fused delta)
+  const int nkt = D == 64 && nkt_env == 2 && !P.drop_thr && !P.kv_lens ? 2 : 1;
   const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nbh = static_cast<unsigned>(B * H);
   const unsigned nk = static_cast<unsigned>((Sk + 128 * nkt - 1) / (128 * nkt));
   dim3 gq = causal ? dim3(nbh, nq) : dim3(nq, nbh), gk = causal ? dim3(nbh, nk) : dim3(nk, nbh), block(256);
@@ -1516,7 +1638,13 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
   const bool fused_delta = fde ? atoi(fde) != 0 : true;
 #define FFK_ATTN_BWD(DD, CC)                                                          \
-  if (P.drop_thr) {                                                                   \
+  if (P.kv_lens && P.drop_thr) {                                                      \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, true, true>), gq, block, 0, st, P);  \
+    launch_dkdv<DD, CC, true, true>(nkt, gk, block, st, P);                           \
+  } else if (P.kv_lens) {                                                             \
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, false, true>), gq, block, 0, st, P); \
+    launch_dkdv<DD, CC, false, true>(nkt, gk, block, st, P);                          \
+  } else if (P.drop_thr) {                                                            \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, true>), gq, block, 0, st, P);\
     launch_dkdv<DD, CC, true>(nkt, gk, block, st, P);                                 \
   } else if (fused_delta) {                                                           \

@@ -100,15 +100,25 @@ struct AttnTensors {
   float drop_keep_scale = 1.f;
   uint64_t seed = 0;
   const int64_t* seed_dev = nullptr;
+  // per-sample key lengths: int32 [B] on the device, 0 <= kv_lens[b] <= Sk
+  // (the kernels clamp).  Keys >= kv_lens[b] of sample b do not exist: they
+  // get probability 0, their K / V rows are never read, and the backward
+  // writes dK = dV = 0 for them.  Read by the kernels, so a captured launch
+  // follows the tensor.  nullptr = every sample has Sk keys (the kernels of a
+  // call without lengths).  With lengths the backward is always the dQ +
+  // dK/dV kernel pair.
+  const int32_t* kv_lens = nullptr;
 };
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st);
 // Returns the path that ran: 1 = the one-pass kernel (D = 64, non-causal,
-// Sk <= 512, no dbias; FFK_ATTN_BWD_ONEPASS=0 turns it off), 0 = the dQ and
+// Sk <= 512, no dbias, no dropout, no key lengths; FFK_ATTN_BWD_ONEPASS=0 turns
+// it off), 0 = the dQ and
 // dK/dV kernels.  With Sk > 256 the one-pass kernel needs `ws`, an fp32
 // scratch of attention_bwd_workspace() floats (0: the call is not eligible
 // or needs none).
-int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias);
+int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias,
+                                bool varlen = false);
 int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                   hipStream_t st, float* ws = nullptr);
 

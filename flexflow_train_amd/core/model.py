@@ -540,13 +540,21 @@ class FFModel:
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
-                            seq_parallel_mode="auto"):
+                            seq_parallel_mode="auto", key_lengths=None):
         """``seq_parallel_mode`` selects the lowering when a strategy shards
-        the sequence dim: "ulysses" (all-to-all), "ring" or "auto"."""
-        return self._add("MULTIHEAD_ATTENTION", [query, key, value], name, (kernel_initializer,),
+        the sequence dim: "ulysses" (all-to-all), "ring" or "auto".
+
+        ``key_lengths``: optional ``DT_INT32`` tensor [batch] of per-sample
+        key lengths (a padding mask): keys at or past ``key_lengths[b]`` do
+        not exist for sample b.  Not available on the sequence-parallel path."""
+        inputs, extra = [query, key, value], {}
+        if key_lengths is not None:
+            inputs.append(key_lengths)
+            extra["key_lengths"] = True
+        return self._add("MULTIHEAD_ATTENTION", inputs, name, (kernel_initializer,),
                          embed_dim=embed_dim, num_heads=num_heads, kdim=kdim, vdim=vdim, dropout=float(dropout),
                          bias=bias, add_bias_kv=add_bias_kv, add_zero_attn=add_zero_attn, causal=causal,
-                         seq_parallel_mode=seq_parallel_mode)
+                         seq_parallel_mode=seq_parallel_mode, **extra)
 
     def experts(self, input, expert_ids, gate_weights, num_experts, hidden_size, out_dim=None,
                 activation=ActiMode.AC_MODE_RELU, use_bias=True, expert_parallel_mode="replicated", name=None):

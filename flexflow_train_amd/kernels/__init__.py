@@ -420,7 +420,25 @@ def _attn_dropout_args(p, seed, seed_dev, q, Sq, Sk):
     return T, int(seed) & ((1 << 64) - 1), _p(seed_dev)
 
 
-def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None):
+def _attn_kv_lens(kv_lens, q):
+    """Pointer of an attention call's per-sample key lengths (0: none).  Only
+    the tensor's metadata is checked: its values are read by the kernels,
+    which clamp them to [0, Sk], so there is no host synchronisation."""
+    if kv_lens is None:
+        return 0
+    if not isinstance(kv_lens, torch.Tensor) or kv_lens.dtype != torch.int32:
+        raise ValueError("attention: kv_lens must be an int32 tensor")
+    if tuple(kv_lens.shape) != (q.shape[0],):
+        raise ValueError(f"attention: kv_lens has shape {tuple(kv_lens.shape)}, expected ({q.shape[0]},)")
+    if kv_lens.device != q.device:
+        raise ValueError("attention: kv_lens must be on the device of q")
+    if not kv_lens.is_contiguous():
+        raise ValueError("attention: kv_lens must be contiguous")
+    STATS["attention_varlen"] += 1
+    return kv_lens.data_ptr()
+
+
+def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None):
     """Flash attention forward.  q,k,v: [B, S, H, D] bf16 views (any b/s/h
     strides, e.g. slices of a packed [B, S, 3, H, D] QKV buffer).
     Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain).
@@ -429,7 +447,14 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     kernel; the mask is that of ``ops.attention.attention_dropout_mask`` for
     the seed ``seed + seed_dev[0]`` (``seed_dev``: optional 1-element int64
     device tensor, read by the kernel, so a captured call follows it).  The
-    LSE is that of the undropped softmax."""
+    LSE is that of the undropped softmax.
+
+    ``kv_lens``: optional int32 [B] device tensor of per-sample key lengths,
+    0 <= kv_lens[b] <= Sk.  Keys >= kv_lens[b] of sample b do not exist: they
+    get probability 0 and their K / V rows are never read, so padding content
+    (NaN included) cannot reach the output.  A row with no live key gives
+    o = 0 and lse = -inf.  The kernels read the tensor, so a captured call
+    follows it."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     if D not in (64, 128):
@@ -437,22 +462,25 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     if k.shape != (B, Sk, H, D) or v.shape != (B, Sk, H, D):
         raise ValueError("attention: q/k/v shape mismatch")
     drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
+    lens = _attn_kv_lens(kv_lens, q)
     if out is None:
         out = torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
     lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
     sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     ext().attention_fwd(_view4(q), _view4(k), _view4(v), _view4(out), lse.data_ptr(), B, H, Sq, Sk, D, sc,
-                        bool(causal), _stream(), *drop)
+                        bool(causal), _stream(), *drop, lens)
     STATS["attention_fwd"] += 1
     return out, lse
 
 
 def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False,
-                  dropout_p=0.0, seed=0, seed_dev=None):
+                  dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None):
     """Flash-attention backward into dq / dk / dv; returns the path that ran
     (1: the one-pass kernel, 0: the dQ and dK/dV kernels).  ``dropout_p``,
     ``seed``, ``seed_dev``: those of the forward call that produced ``o``
-    (dropout always takes path 0).  ``dbias`` = optional
+    (dropout always takes path 0).  ``kv_lens``: the forward call's key
+    lengths (always path 0); dk / dv rows past a sample's length are written
+    as zeros.  ``dbias`` = optional
     (dbq, dbk, dbv) fp32 [H*D] projection-bias gradients, accumulated with the
     column sums of dq / dk / dv (over batch and sequence) computed in the
     kernels' epilogues: by default each wave stores its 32-row partial into a
@@ -484,11 +512,13 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     # the one-pass kernel (D = 64, non-causal, Sk <= 512, no dbias) keeps the
     # first key block's dQ in an fp32 scratch when there is a second one
     drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
-    n_ws = 0 if drop[0] else ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal), dbias is not None)
+    lens = _attn_kv_lens(kv_lens, q)
+    n_ws = 0 if drop[0] else ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal), dbias is not None,
+                                                            bool(lens))
     ws = torch.empty(n_ws, device=q.device, dtype=torch.float32) if n_ws else None
     path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
                                _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
-                               _stream(), *dbs, ld, _p(ws), *drop)
+                               _stream(), *dbs, ld, _p(ws), *drop, lens)
     if path == 1:
         STATS["attention_bwd_onepass"] += 1
     if slab is not None:

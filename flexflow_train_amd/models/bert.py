@@ -40,6 +40,9 @@ class BertConfig:
     embeddings: bool = True          # False -> hidden-state input like the reference graph
     mlm_transform: bool = True
     pad_vocab_to: int = 64
+    # True: an int32 input `seq_lens` [batch] carries every sample's true
+    # length; keys at or past it do not exist for any layer's attention
+    key_lengths: bool = False
 
     @property
     def padded_vocab(self) -> int:
@@ -80,11 +83,15 @@ def build_bert(model: FFModel, cfg: BertConfig) -> Tuple[Dict[str, object], obje
     else:
         x = model.create_tensor([B, S, E], DataType.DT_FLOAT, create_grad=True, name="hidden_input")
         inputs["hidden_input"] = x
+    lens = None
+    if cfg.key_lengths:
+        lens = model.create_tensor([B], DataType.DT_INT32, create_grad=False, name="seq_lens")
+        inputs["seq_lens"] = lens
     act = ActiMode.AC_MODE_GELU if cfg.hidden_act == "gelu" else ActiMode.AC_MODE_RELU
     for i in range(cfg.num_encoder_layers):
         pre = f"encoder.{i}"
         a = model.multihead_attention(x, x, x, E, cfg.num_heads, dropout=cfg.attention_probs_dropout_prob,
-                                      bias=True, kernel_initializer=proj_init, name=f"{pre}.attn")
+                                      bias=True, kernel_initializer=proj_init, name=f"{pre}.attn", key_lengths=lens)
         if cfg.hidden_dropout_prob > 0:
             a = model.dropout(a, cfg.hidden_dropout_prob, i, name=f"{pre}.attn_dropout")
         x = model.layer_norm(model.add(a, x, name=f"{pre}.attn_residual"), [-1], True, cfg.layer_norm_eps,

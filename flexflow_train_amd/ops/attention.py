@@ -16,6 +16,13 @@ epilogue); output bias [E] is added on partial-sum replica 0 only.
 The fused QKV output [B, S, 3, Hl, k] is consumed by the flash kernel in
 place (strided views), and dQKV is produced in the same packed layout, so the
 backward needs exactly one GEMM for dW_qkv and one for dX.
+
+Key lengths (optional fourth input, an integer tensor [B]): keys >= lens[b] of
+sample b do not exist.  They get probability 0, dK = dV = 0, and their K / V
+rows are never read, so padding content (NaN included) cannot reach an output;
+a row without a live key gives o = 0 and dQ = 0.  The flash kernels read the
+lengths from the device tensor (a captured step follows a new batch's lengths);
+the torch fallback applies the same definition as a mask.
 """
 from __future__ import annotations
 
@@ -75,15 +82,30 @@ def _split_weights(W, E, Hl, kd, vd, Eq, Ek, Ev):
     return {"q": Wq, "k": Wk, "v": Wv, "o": Wo}
 
 
-def _torch_attention(q, k, v, causal, scale, drop=None):
+def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None):
     # q,k,v: [B, S, H, D] -> [B, S, H, D]; drop = (keep mask [B, H, Sq, Sk], keep scale)
+    # kv_lens: [B] integer key lengths (module docstring)
     qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
+    dead = None
+    if kv_lens is not None:
+        Sk = k.shape[1]
+        dead = torch.arange(Sk, device=k.device).view(1, Sk) >= kv_lens.view(-1, 1).clamp(0, Sk)  # [B, Sk]
+        # dead K / V rows are never read: zeros in their place, so that neither
+        # 0 * NaN in the products nor their gradients can carry padding content
+        kt = kt.masked_fill(dead[:, None, :, None], 0)
+        vt = vt.masked_fill(dead[:, None, :, None], 0)
     s = torch.matmul(qt.float(), kt.float().transpose(-1, -2)) * scale
+    if dead is not None:
+        s = s.masked_fill(dead[:, None, None, :], float("-inf"))
+        # a row with no live key: finite scores for the softmax, zeroed below
+        s = s.masked_fill(dead.all(-1)[:, None, None, None], 0.0)
     if causal:
         Sq, Sk = s.shape[-2:]
         mask = torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1)
         s = s.masked_fill(mask, float("-inf"))
     p = torch.softmax(s, -1)
+    if dead is not None:
+        p = p.masked_fill(dead[:, None, None, :], 0.0)
     if drop is not None:
         p = p * drop[0].to(p.dtype) * drop[1]
     return torch.matmul(p, vt.float()).transpose(1, 2).to(q.dtype)
@@ -272,7 +294,14 @@ class MultiHeadAttentionOp(OpImpl):
         return (1, 0.0, math.sqrt(2.0 / (E + H * kd)), 0.0, 0.0)
 
     def forward(self, ctx: OpContext, inputs, weights):
-        q_in, k_in, v_in = inputs
+        q_in, k_in, v_in = inputs[:3]
+        lens = None
+        if len(inputs) > 3:  # per-sample key lengths
+            lens = inputs[3].reshape(-1)
+            if lens.dtype.is_floating_point or lens.shape[0] != q_in.shape[0]:
+                raise ValueError(f"{ctx.name}: key lengths must be an integer tensor [batch], got "
+                                 f"{lens.dtype} {tuple(inputs[3].shape)}")
+            lens = lens.to(torch.int32).contiguous()
         W = weights[0]
         b_in = weights[1] if len(weights) > 1 else None
         b_out = weights[2] if len(weights) > 2 and ctx.sum_index == 0 else None
@@ -306,6 +335,9 @@ class MultiHeadAttentionOp(OpImpl):
         p_drop = float(ctx.a("dropout", 0.0) or 0.0) if ctx.training else 0.0
         drop = None
         if grp is not None and grp.size > 1:
+            if lens is not None:
+                raise NotImplementedError(f"{ctx.name}: key lengths are not supported on the sequence-parallel "
+                                          "(ring / Ulysses) attention path")
             if p_drop > 0 and not ctx.extra.get("attn_drop_warned"):
                 ctx.extra["attn_drop_warned"] = True
                 warnings.warn(f"{ctx.name}: attention dropout is not applied on the sequence-parallel path")
@@ -317,17 +349,18 @@ class MultiHeadAttentionOp(OpImpl):
                 drop = (p_drop, _drop_seed(ctx), _drop_step(ctx, q.device))
             if use_flash:
                 kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
-                o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale, **kw)
+                o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale, kv_lens=lens, **kw)
             else:
-                o, lse = _torch_attention(q, k, v, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk)), None
+                o, lse = _torch_attention(q, k, v, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens), None
         o2 = o.reshape(B * Sq, Hl * vd)
         out = matmul(o2, ws["o"], bias=b_out)
         saved = (x2, k_in if not self_attn else None, v_in if not self_attn else None, proj, o, lse, ws,
-                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale), drop)
+                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale), lens, drop)
         return [out.view(B, Sq, E)], saved
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
-        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims, drop = saved
+        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims, lens, drop = saved
+        no_lens_grad = [None] if lens is not None else []   # the lengths input gets no gradient
         B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale = dims
         dW = weight_grads[0]
         db_in = weight_grads[1] if len(weight_grads) > 1 else None
@@ -379,12 +412,13 @@ class MultiHeadAttentionOp(OpImpl):
                 n = Hl * kd
                 fused_db = (dbf[:n], dbf[n:2 * n], dbf[2 * n:3 * n])
             kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
-            K.attention_bwd(q, k, v, o, lse, do4, dq, dk, dv, causal=causal, scale=scale, dbias=fused_db, **kw)
+            K.attention_bwd(q, k, v, o, lse, do4, dq, dk, dv, causal=causal, scale=scale, dbias=fused_db,
+                            kv_lens=lens, **kw)
             if fused_db is not None:
                 db_in = None   # accumulated by the attention backward kernels
         else:
             qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-            ref = _torch_attention(qf, kf, vf, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk))
+            ref = _torch_attention(qf, kf, vf, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens)
             ref.float().backward(do4.float())
             dq, dk, dv = (t.grad.to(do.dtype) for t in (qf, kf, vf))
             if self_attn:
@@ -407,9 +441,9 @@ class MultiHeadAttentionOp(OpImpl):
                 acc = ctx.extra.get("grad_acc", [None])[0]
                 if gpu and acc is not None and acc.dtype == d2.dtype and acc.is_contiguous():
                     matmul(d2, ws["qkv"], trans_b=True, out=acc.view(B * Sq, Eq), beta=1.0)
-                    return [acc, None, None]
+                    return [acc, None, None] + no_lens_grad
                 dx_q = (matmul(d2, ws["qkv"], trans_b=True) if gpu else d2 @ ws["qkv"].to(d2.dtype).t()).view(B, Sq, Eq)
-            return [dx_q, None, None]
+            return [dx_q, None, None] + no_lens_grad
         srcs = ((x2, dq, "q", Eq, Sq, kd), (k_in.reshape(-1, Ek).contiguous(), dk, "k", Ek, Sk, kd),
                 (v_in.reshape(-1, Ev).contiguous(), dv, "v", Ev, Sk, vd))
         outs = []
@@ -428,4 +462,4 @@ class MultiHeadAttentionOp(OpImpl):
                 outs.append(dxx.view(B, S, Ein))
             else:
                 outs.append(None)
-        return outs
+        return outs + no_lens_grad

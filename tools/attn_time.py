@@ -6,6 +6,7 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
     python tools/attn_time.py [iters]
     python tools/attn_time.py --pipe-ab | --delta-ab | --onepass-ab   (same-process A/B of a kernel switch)
     python tools/attn_time.py --dropout 0.1                           (attention dropout against p = 0)
+    python tools/attn_time.py --varlen [--dropout 0.1]                (per-sample key lengths against full length)
 """
 import json
 import os
@@ -122,7 +123,55 @@ def dropout_ab(p, iters, rounds=5):
         print(json.dumps(rec), flush=True)
 
 
+def varlen_ab(iters, rounds=5, seed=0, p=0.0):
+    """Interleaved same-process timing of the forward and the backward with
+    per-sample key lengths drawn uniformly from [Sk / 8, Sk] (fixed seed)
+    against the same call without lengths, and against lengths all equal to
+    Sk (the cost of the length-aware kernels alone).  With lengths the
+    backward is the dQ + dK/dV kernel pair at every shape.  `p` > 0 adds
+    attention dropout to all three variants (`--varlen --dropout p`): "full"
+    against "none" is then the cost of the forms with lengths and dropout,
+    whose dQ kernel takes delta from the probabilities.  `live_tiles` is
+    the fraction of 64-key tiles with a live key (the causal shapes count the
+    tiles at or below the diagonal of each 128-query block only)."""
+    import statistics
+    for name, (B, S, H, D, causal) in SHAPES.items():
+        g = torch.Generator(device="cuda").manual_seed(0)
+        qkv = torch.randn(B, S, 3, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+        do = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        dqkv = torch.empty_like(qkv)
+        lens_cpu = torch.randint(S // 8, S + 1, (B,), generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
+        variants = {"none": None, "full": torch.full((B,), S, device="cuda", dtype=torch.int32),
+                    "varlen": lens_cpu.cuda()}
+        live = total = 0
+        for n in lens_cpu.tolist():
+            for qb in range((S + 127) // 128):
+                cap = min((S + 63) // 64, (qb * 128 + 128 + 63) // 64) if causal else (S + 63) // 64
+                total += cap
+                live += min(cap, (n + 63) // 64)
+        t = {}
+        for _ in range(rounds):
+            for tag, lens in variants.items():
+                kw = dict(causal=causal, kv_lens=lens, dropout_p=p, seed=1234)
+                o, lse = K.attention_fwd(q, k, v, **kw)
+                t.setdefault(("fwd", tag), []).append(_time(lambda: K.attention_fwd(q, k, v, out=o, **kw), iters))
+                t.setdefault(("bwd", tag), []).append(_time(
+                    lambda: K.attention_bwd(q, k, v, o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], **kw),
+                    iters))
+        med = {key: statistics.median(x) for key, x in t.items()}
+        rec = {"shape": name, "seed": seed, "dropout": p, "mean_len": round(float(lens_cpu.float().mean()), 1),
+               "live_tiles": round(live / total, 4)}
+        for which in ("fwd", "bwd"):
+            for tag in variants:
+                rec[f"{which}_ms_{tag}"] = round(med[(which, tag)], 4)
+                rec[f"{which}_rounds_{tag}"] = [round(x, 4) for x in t[(which, tag)]]
+        print(json.dumps(rec), flush=True)
+
+
 def main():
+    if "--varlen" in sys.argv:         # per-sample key lengths against full length
+        return varlen_ab(30, p=float(sys.argv[sys.argv.index("--dropout") + 1]) if "--dropout" in sys.argv else 0.0)
     if "--dropout" in sys.argv:        # attention dropout against p = 0, forward and backward
         return dropout_ab(float(sys.argv[sys.argv.index("--dropout") + 1]), 30)
     if "--pmc-run" in sys.argv:
