@@ -580,7 +580,12 @@ OpSpec embedding_spec() {
 // per-sample key lengths: rank 1 [batch], an integer dtype.  Keys at or past a
 // sample's length do not exist for that sample.  The attribute is absent from
 // a 3-input node (no default), so graphs without lengths serialise as before.
+// With query_lengths = true as well, the same input also gives each sample's
+// query length (self-attention over a padded batch): queries at or past it do
+// not exist either.  One tensor bounds both axes, so it needs key_lengths and
+// equal query and key sequence extents.  Absent by default, like key_lengths.
 bool mha_has_lengths(const OpAttrs& a) { return a.has("key_lengths") && a.b("key_lengths"); }
+bool mha_has_query_lengths(const OpAttrs& a) { return a.has("query_lengths") && a.b("query_lengths"); }
 bool is_integer_dtype(DataType t) { return t == DataType::INT32 || t == DataType::INT64; }
 
 OpSpec mha_spec() {
@@ -614,6 +619,11 @@ OpSpec mha_spec() {
     }
     require(in[0].dims[0] == in[1].dims[0] && in[0].dims[0] == in[2].dims[0], a, "batch mismatch");
     require(in[1].dims[1] == in[2].dims[1], a, "key/value sequence length mismatch");
+    if (mha_has_query_lengths(a)) {
+      require(mha_has_lengths(a), a, "query_lengths needs key_lengths (the lengths input bounds both axes)");
+      require(in[0].dims[1] == in[1].dims[1], a,
+              "query_lengths needs equal query and key sequence extents: one lengths tensor bounds both axes");
+    }
     return Shapes{TensorShape{{in[0].dims[0], in[0].dims[1], a.i("embed_dim")}, in[0].dtype}};
   };
   s.wts = [kd, vd](const OpAttrs& a, const Shapes& in) {

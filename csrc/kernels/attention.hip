@@ -65,6 +65,21 @@
 // rows keep the physical Sk.  The backward with lengths is the dQ + dK/dV
 // pair; a call without lengths runs the VARLEN = false kernels, in which the
 // bound is P.Sk as before.
+//
+// Per-sample query lengths (the same VARLEN instantiations;
+// AttnTensors::q_lens, int32 [B] on the device, clamped to [0, Sq]).  Queries
+// >= q_lens[b] do not exist for sample b, with the definitions of the key
+// axis mirrored: o = 0, lse = -inf and dQ = 0 are stored for every dead row
+// below the physical Sq, a dead row adds nothing to dK, dV or the dbias
+// partials, and Q, O, dO, lse and delta of a dead row are never read.  A
+// forward / dQ workgroup whose 128-query block is wholly dead stores its
+// zeros and returns before the tile loop (a workgroup-uniform exit ahead of
+// the first barrier); a wholly dead wave of a live block stages tiles and
+// meets the barriers without MFMAs, like an inactive causal wave; dead rows
+// of a live wave load zeros and are masked.  The dK/dV kernel's query-tile
+// loop ends at the last live tile.  Either pointer may be null in a VARLEN
+// kernel: null means the physical extent.  The dropout hash index and the
+// dbias slab rows keep their physical positions.
 #include <cstdlib>
 
 #include "kernels.h"
@@ -100,6 +115,7 @@ struct AttnParams {
   const int64_t* seed_dev;  // optional device-resident addend of the seed
   // per-sample key lengths (VARLEN kernels only; appended like the dropout fields)
   const int32_t* kv_lens;   // [B]; keys >= kv_lens[b] of sample b do not exist
+  const int32_t* q_lens;    // [B]; queries >= q_lens[b] of sample b do not exist
 };
 
 // Key-axis bound of sample b.  VARLEN: the sample's own length, read from the
@@ -109,8 +125,24 @@ struct AttnParams {
 // The dropout hash index keeps the physical Sk as its row stride either way.
 template <bool VARLEN>
 __device__ __forceinline__ int key_len(const AttnParams& P, int b) {
-  if constexpr (VARLEN) return __builtin_amdgcn_readfirstlane(min(max(P.kv_lens[b], 0), P.Sk));
+  if constexpr (VARLEN) return P.kv_lens ? __builtin_amdgcn_readfirstlane(min(max(P.kv_lens[b], 0), P.Sk)) : P.Sk;
   else return P.Sk;
+}
+// Query-axis bound of sample b, the same way: q_lens[b] clamped to [0, Sq] in
+// a VARLEN kernel that was given query lengths, otherwise the physical Sq.
+template <bool VARLEN>
+__device__ __forceinline__ int query_len(const AttnParams& P, int b) {
+  if constexpr (VARLEN) return P.q_lens ? __builtin_amdgcn_readfirstlane(min(max(P.q_lens[b], 0), P.Sq)) : P.Sq;
+  else return P.Sq;
+}
+
+// A wave's 32 dead query rows (lane & 31 -> row, lane half h -> the row's odd
+// or even 16-byte chunks) stored as zeros: the output of a workgroup that
+// leaves before its tile loop.
+template <int D>
+__device__ __forceinline__ void store_zero_rows(bf16* row, int h) {
+#pragma unroll
+  for (int c = 0; c < D / 16; ++c) *reinterpret_cast<u32x4t*>(row + (2 * c + h) * 8) = u32x4t{0u, 0u, 0u, 0u};
 }
 
 // Dropout hash (definition in the header comment).  drop_key is uniform over
@@ -311,12 +343,24 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   const int q = qw + (lane & 31);
   const bool q_ok = q < P.Sq;
   const int Skl = key_len<VARLEN>(P, b);  // keys of this sample
+  // queries of this sample: q_live rows exist, q_ok rows have an output row
+  [[maybe_unused]] const int Sql = query_len<VARLEN>(P, b);
+  const bool q_live = VARLEN ? q < Sql : q_ok;
+  if constexpr (VARLEN) {
+    if (q_blk >= Sql) {  // a wholly dead block: o = 0, lse = -inf, no tile loop
+      if (q_ok) {
+        store_zero_rows<D>(P.o_out + b * P.o_sb + static_cast<int64_t>(q) * P.o_ss + hh * P.o_sh, h);
+        if (h == 0) P.lse[static_cast<int64_t>(bh) * P.Sq + q] = -INFINITY;
+      }
+      return;
+    }
+  }
 
   // Q as the B operand of S^T = K Q^T: lane holds Q[q][16ks + 8h .. +8]
   bf16x8 qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
-    qf[ks] = q_ok ? *reinterpret_cast<const bf16x8*>(P.q.p + b * P.q.sb + static_cast<int64_t>(q) * P.q.ss +
+    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.p + b * P.q.sb + static_cast<int64_t>(q) * P.q.ss +
                                                      hh * P.q.sh + ks * 16 + 8 * h)
                   : bf16x8{};
 
@@ -341,6 +385,24 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   vl.store(smem + TILE_BYTES);
   __syncthreads();
 
+  // VARLEN: a wave whose 32 rows are all dead (in a block with live rows)
+  // stages its share of every tile and meets the barriers, nothing else, in a
+  // loop of its own: the branch is taken once, outside the tile loop below
+  if constexpr (VARLEN) {
+    if (__builtin_amdgcn_readfirstlane(qw) >= Sql) {
+      for (int t = 0; t < n_tiles; ++t) {
+        if (t + 1 < n_tiles) {
+          kl.load(P.k, b, hh, (t + 1) * KV, Skl);
+          vl.load(P.v, b, hh, (t + 1) * KV, Skl);
+          unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
+          kl.store(nxt);
+          vl.store(nxt + TILE_BYTES);
+        }
+        __syncthreads();
+      }
+      n_tiles = 0;  // nothing left for the tile loop
+    }
+  }
   for (int t = 0; t < n_tiles; ++t) {
     const int k0 = t * KV;
     const unsigned char* Kt = smem + (t & 1) * 2 * TILE_BYTES;
@@ -444,7 +506,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   }
 
   // ---- epilogue: O = O^T / l, LSE
-  const float lt = l + __shfl_xor(l, 32, 64);
+  float lt = l + __shfl_xor(l, 32, 64);
+  if constexpr (VARLEN) {
+    // a dead row of a live wave ran on Q = 0: no row sum, and a clean zero
+    if (!q_live) {
+      lt = 0.f;
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt) o[dt] = f32x16{};
+    }
+  }
   float inv = lt > 0.f ? 1.f / lt : 0.f;
   if constexpr (DROP) inv *= P.drop_rs;
   bf16* orow = P.o_out + b * P.o_sb + static_cast<int64_t>(q) * P.o_ss + hh * P.o_sh;
@@ -687,25 +757,38 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   const int q = qw + (lane & 31);
   const bool q_ok = q < P.Sq;
   const int Skl = key_len<VARLEN>(P, b);  // keys of this sample
+  // queries of this sample: q_live rows exist, q_ok rows have a dQ row
+  [[maybe_unused]] const int Sql = query_len<VARLEN>(P, b);
+  const bool q_live = VARLEN ? q < Sql : q_ok;
+  if constexpr (VARLEN) {
+    if (q_blk >= Sql) {  // a wholly dead block: dQ = 0 and zero dbias partials, no tile loop
+      if (q_ok) store_zero_rows<D>(P.dq + b * P.dq_sb + static_cast<int64_t>(q) * P.dq_ss + hh * P.dq_sh, h);
+      if (P.dbq && P.db_ld && qw < P.Sq) {
+        float* drow = P.dbq + (static_cast<int64_t>(b) * ((P.Sq + 31) / 32) + qw / 32) * P.db_ld + hh * D;
+        for (int c = lane; c < D; c += 64) drow[c] = 0.f;
+      }
+      return;
+    }
+  }
 
   bf16x8 qf[KS], df[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    qf[ks] = q_ok ? *reinterpret_cast<const bf16x8*>(P.q.p + b * P.q.sb + static_cast<int64_t>(q) * P.q.ss +
+    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.p + b * P.q.sb + static_cast<int64_t>(q) * P.q.ss +
                                                      hh * P.q.sh + ks * 16 + 8 * h)
                   : bf16x8{};
-    df[ks] = q_ok ? *reinterpret_cast<const bf16x8*>(P.dout.p + b * P.dout.sb +
+    df[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.dout.p + b * P.dout.sb +
                                                      static_cast<int64_t>(q) * P.dout.ss + hh * P.dout.sh +
                                                      ks * 16 + 8 * h)
                   : bf16x8{};
   }
-  const float lse = q_ok ? P.lse[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
+  const float lse = q_live ? P.lse[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
   float dlt;
   if constexpr (FUSED_DELTA) {
     // lane (q, h) holds d = 16 ks + 8 h .. +8 of dO row q: a partial dot over
     // those, then the other half from lane ^ 32
     float part = 0.f;
-    if (q_ok) {
+    if (q_live) {
 #pragma unroll
       for (int ks = 0; ks < KS; ++ks) {
         const bf16x8 of = *reinterpret_cast<const bf16x8*>(P.o.p + b * P.o.sb + static_cast<int64_t>(q) * P.o.ss +
@@ -716,9 +799,9 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     }
     dlt = part + __shfl_xor(part, 32, 64);
     if constexpr (!XDELTA)  // XDELTA writes the exact delta after the loop
-      if (q_ok && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = dlt;
+      if (q_live && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = dlt;
   } else {
-    dlt = q_ok ? P.delta[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
+    dlt = q_live ? P.delta[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
   }
 
   f32x16 dq[DT];
@@ -756,7 +839,33 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   vl.store(smem + TILE_BYTES);
   __syncthreads();
 
-  for (int t = 0; t < n_tiles; ++t) {
+  // VARLEN: a wholly dead wave of a live block stages tiles and meets the
+  // barriers in a loop of its own (see the forward).  The tile loop is then
+  // left out through its bound (D = 64) or through its start (D = 128): two
+  // spellings of one thing that the register allocator tells apart.  At
+  // D = 64 the bound form compiles to the allocation these kernels had before
+  // they knew query lengths, and to their times; at D = 128 the causal form
+  // with dropout (512 registers) reloads 7 spilled values per tile with it,
+  // one more than before, and none with the start form.
+  constexpr bool SKIP_BY_START = VARLEN && D == 128;
+  [[maybe_unused]] int t_first = 0;
+  if constexpr (VARLEN) {
+    if (__builtin_amdgcn_readfirstlane(qw) >= Sql) {
+      for (int t = 0; t < n_tiles; ++t) {
+        if (t + 1 < n_tiles) {
+          kl.load(P.k, b, hh, (t + 1) * KV, Skl);
+          vl.load(P.v, b, hh, (t + 1) * KV, Skl);
+          unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
+          kl.store(nxt);
+          vl.store(nxt + TILE_BYTES);
+        }
+        __syncthreads();
+      }
+      if constexpr (SKIP_BY_START) t_first = n_tiles;
+      else n_tiles = 0;
+    }
+  }
+  for (int t = SKIP_BY_START ? t_first : 0; t < n_tiles; ++t) {
     const int k0 = t * KV;
     const unsigned char* Kt = smem + (t & 1) * 2 * TILE_BYTES;
     const unsigned char* Vt = Kt + TILE_BYTES;
@@ -766,7 +875,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
       vl.load(P.v, b, hh, k0 + KV, Skl);
     }
     const bool wave_active = !CAUSAL || (k0 <= qw + 31);
-    const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= P.Sq);
+    const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= (VARLEN ? Sql : P.Sq));
     if (wave_active) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
@@ -785,7 +894,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             float pv = fexp2(s[r] * P.scale_log2 - lse);
-            if (key >= Skl || (CAUSAL && key > q) || !q_ok) pv = 0.f;
+            if (key >= Skl || (CAUSAL && key > q) || !q_live) pv = 0.f;
             if constexpr (XDELTA) {
               const float kd = kept(dp[r], k0, kt, r);
               pf[r >> 3][r & 7] = f2bf(pv);
@@ -842,7 +951,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) dq[dt][r] = fmaf(c, bq[dt][r], dq[dt][r]);
-    if (q_ok && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = delta;
+    if (q_live && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = delta;
   }
   if (P.dbq && P.db_ld) {
     if (qw < P.Sq)  // waves wholly past the sequence own no slab row
@@ -904,6 +1013,14 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
     if constexpr (VARLEN) return len_v;
     else return P.Sk;
   };
+  // queries of this sample, the same way: every bound on the query axis (the
+  // tile count, the tile loads, the parked -lse / c, the masks) takes it
+  [[maybe_unused]] int qlen_v = 0;
+  if constexpr (VARLEN) qlen_v = query_len<true>(P, b);
+  auto Sql = [&]() -> int {
+    if constexpr (VARLEN) return qlen_v;
+    else return P.Sq;
+  };
 
   // K, V rows as B operands (lane holds row `key`, d = 16ks + 8h ..)
   bf16x8 kf[NKT][KS], vf[NKT][KS];
@@ -934,8 +1051,9 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
     for (int dt = 0; dt < DT; ++dt) dk[j][dt] = dv[j][dt] = f32x16{};
 
   // VARLEN: a key block wholly past the length skips the query loop and
-  // stores zeros (dK = dV = 0, and zero partials into the dbias slab)
-  const int n_q_tiles = (VARLEN && k_blk >= Skl()) ? 0 : (P.Sq + QT - 1) / QT;
+  // stores zeros (dK = dV = 0, and zero partials into the dbias slab); the
+  // loop of a live block ends at the sample's last live query tile
+  const int n_q_tiles = (VARLEN && k_blk >= Skl()) ? 0 : (Sql() + QT - 1) / QT;
   const int t0 = CAUSAL ? (k_blk / QT) : 0;
   // dropout: hash index of register r of a subtile = (first query + 4 h +
   // (r & 3) + 8 (r >> 2)) * Sk + key
@@ -961,7 +1079,10 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
   bool nok = false;
   auto fetch_scalars = [&](int q0) {
     const int qq = q0 + threadIdx.x;
-    nok = threadIdx.x < QT && qq < P.Sq;
+    // not through Sql(): capturing that lambda here renamed two registers in
+    // the causal VARLEN = false forms, which are to stay the code they were
+    if constexpr (VARLEN) nok = threadIdx.x < QT && qq < qlen_v;
+    else nok = threadIdx.x < QT && qq < P.Sq;
     if (nok) {
       nls = P.lse[static_cast<int64_t>(bh) * P.Sq + qq];
       nds = P.delta[static_cast<int64_t>(bh) * P.Sq + qq];
@@ -980,8 +1101,8 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
   // vmcnt(0), so the first MFMA of EVERY iteration waited on vmcnt — and
   // vmcnt retires in order, so that wait drained the next tile's prefetch
   // right after issuing it (one exposed global-load latency per tile)
-  ql.load(P.q, b, hh, t0 * QT, P.Sq);
-  dl.load(P.dout, b, hh, t0 * QT, P.Sq);
+  ql.load(P.q, b, hh, t0 * QT, Sql());
+  dl.load(P.dout, b, hh, t0 * QT, Sql());
   fetch_scalars(t0 * QT);
   ql.store(smem);
   dl.store(smem + TILE_BYTES);
@@ -997,12 +1118,12 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
     const float* ds = ls + QT;
     const bool has_next = t + 1 < n_q_tiles;
     if (has_next) {
-      ql.load(P.q, b, hh, q0 + QT, P.Sq);
-      dl.load(P.dout, b, hh, q0 + QT, P.Sq);
+      ql.load(P.q, b, hh, q0 + QT, Sql());
+      dl.load(P.dout, b, hh, q0 + QT, Sql());
       fetch_scalars(q0 + QT);
     }
     const bool wave_active = !CAUSAL || (q0 + QT - 1 >= kw);
-    const bool need_mask = (q0 + QT > P.Sq) || (CAUSAL && q0 < kw + KW - 1) || (kw + KW - 1 >= Skl());
+    const bool need_mask = (q0 + QT > Sql()) || (CAUSAL && q0 < kw + KW - 1) || (kw + KW - 1 >= Skl());
     if (wave_active) {
       // DROP at D = 128 (all 512 registers in use): the fragment offsets of
       // the per-pair reads are derived from the lane id again in every tile.
@@ -1074,7 +1195,7 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
               const int rq = (r & 3) + 8 * (r >> 2);
               const int qq = q0 + qt * 32 + rq + 4 * h;
               float pv = fexp2(s[j][r] * P.scale_log2);
-              if (need_mask && (qq >= P.Sq || (CAUSAL && key[j] > qq) || !k_ok[j])) pv = 0.f;
+              if (need_mask && (qq >= Sql() || (CAUSAL && key[j] > qq) || !k_ok[j])) pv = 0.f;
               const bool drop =
                   dropped(dq0 + static_cast<unsigned>(rq) * static_cast<unsigned>(P.Sk), dkey, P.drop_thr);
               dp[j][r] = pv * fmaf(drop ? 0.f : P.drop_rs, dp[j][r], ds[qt * 32 + rq + 4 * h]);
@@ -1085,7 +1206,7 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
             for (int r = 0; r < 16; ++r) {
               const int qq = q0 + qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
               float pv = fexp2(s[j][r] * P.scale_log2);
-              if (qq >= P.Sq || (CAUSAL && key[j] > qq) || !k_ok[j]) pv = 0.f;
+              if (qq >= Sql() || (CAUSAL && key[j] > qq) || !k_ok[j]) pv = 0.f;
               s[j][r] = pv;
               dp[j][r] = pv * dp[j][r];
             }
@@ -1503,6 +1624,7 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
     P.seed_dev = t.seed_dev;
   }
   P.kv_lens = t.kv_lens;
+  P.q_lens = t.q_lens;
   return P;
 }
 
@@ -1518,7 +1640,7 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
   // in-wave overlap gains
   const char* pe = getenv("FFK_ATTN_FWD_PIPE");
   const int pipe = pe ? atoi(pe) : 0;
-  if (P.kv_lens) {  // key lengths: the default variant only, like dropout
+  if (P.kv_lens || P.q_lens) {  // key / query lengths: the default variant only, like dropout
 #define FFK_ATTN_FWD_VL(DD, CC)                                                                  \
   if (P.drop_thr) hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, true, true>), grid, block, 0, st, P); \
   else hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, false, true>), grid, block, 0, st, P)
@@ -1612,7 +1734,7 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
   // a second key block needs the workspace: callers that pass none keep the
   // two-kernel path
-  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv, P.drop_thr != 0, P.kv_lens != nullptr) &&
+  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv, P.drop_thr != 0, P.kv_lens || P.q_lens) &&
       (Sk <= 256 || ws)) {
     hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(static_cast<unsigned>(B * H)), dim3(512), 0, st, P, ws);
     FFK_LAUNCH_CHECK("attention_bwd");
@@ -1628,9 +1750,10 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   // NKT = 2 (64 keys per wave) halves LDS reads per MFMA but needs ~500
   // registers (1 wave/SIMD, spills when causal): measured 0.24 vs 0.21 ms
   // (BERT shape) and 0.92 vs 0.56 ms (GPT causal) — opt-in only.
-  // (dropout and key lengths: the default variants only, NKT = 1 and the
-  // fused delta)
-  const int nkt = D == 64 && nkt_env == 2 && !P.drop_thr && !P.kv_lens ? 2 : 1;
+  // (dropout and key / query lengths: the default variants only, NKT = 1 and
+  // the fused delta)
+  const bool varlen = P.kv_lens || P.q_lens;
+  const int nkt = D == 64 && nkt_env == 2 && !P.drop_thr && !varlen ? 2 : 1;
   const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nbh = static_cast<unsigned>(B * H);
   const unsigned nk = static_cast<unsigned>((Sk + 128 * nkt - 1) / (128 * nkt));
   dim3 gq = causal ? dim3(nbh, nq) : dim3(nq, nbh), gk = causal ? dim3(nbh, nk) : dim3(nk, nbh), block(256);
@@ -1638,10 +1761,10 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
   const bool fused_delta = fde ? atoi(fde) != 0 : true;
 #define FFK_ATTN_BWD(DD, CC)                                                          \
-  if (P.kv_lens && P.drop_thr) {                                                      \
+  if (varlen && P.drop_thr) {                                                         \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, true, true>), gq, block, 0, st, P);  \
     launch_dkdv<DD, CC, true, true>(nkt, gk, block, st, P);                           \
-  } else if (P.kv_lens) {                                                             \
+  } else if (varlen) {                                                                \
     hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, false, true>), gq, block, 0, st, P); \
     launch_dkdv<DD, CC, false, true>(nkt, gk, block, st, P);                          \
   } else if (P.drop_thr) {                                                            \

@@ -143,7 +143,7 @@ PYBIND11_MODULE(_ffkernels, m) {
   });
   m.def("attention_fwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, uintptr_t lse, int B, int H, int Sq,
                             int Sk, int D, float scale, bool causal, uintptr_t st, uint32_t drop_t, uint64_t seed,
-                            uintptr_t seed_dev, uintptr_t kv_lens) {
+                            uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens) {
     AttnTensors t;
     t.q = tview(q);
     t.k = tview(k);
@@ -152,15 +152,17 @@ PYBIND11_MODULE(_ffkernels, m) {
     t.lse = F(lse);
     set_dropout(t, drop_t, seed, seed_dev);
     t.kv_lens = reinterpret_cast<const int32_t*>(kv_lens);
+    t.q_lens = reinterpret_cast<const int32_t*>(q_lens);
     attention_fwd(t, B, H, Sq, Sk, D, scale, causal, S(st));
   }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("B"), py::arg("H"),
         py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"),
-        py::arg("drop_t") = 0, py::arg("seed") = 0, py::arg("seed_dev") = 0, py::arg("kv_lens") = 0);
+        py::arg("drop_t") = 0, py::arg("seed") = 0, py::arg("seed_dev") = 0, py::arg("kv_lens") = 0,
+        py::arg("q_lens") = 0);
   m.def("attention_bwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, py::tuple dout, py::tuple dq,
                             py::tuple dk, py::tuple dv, uintptr_t lse, uintptr_t delta, int B, int H, int Sq, int Sk,
                             int D, float scale, bool causal, uintptr_t st, uintptr_t dbq, uintptr_t dbk,
                             uintptr_t dbv, int64_t db_ld, uintptr_t ws, uint32_t drop_t, uint64_t seed,
-                            uintptr_t seed_dev, uintptr_t kv_lens) {
+                            uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens) {
     AttnTensors t;
     t.q = tview(q);
     t.k = tview(k);
@@ -178,12 +180,13 @@ PYBIND11_MODULE(_ffkernels, m) {
     t.db_ld = db_ld;
     set_dropout(t, drop_t, seed, seed_dev);
     t.kv_lens = reinterpret_cast<const int32_t*>(kv_lens);
+    t.q_lens = reinterpret_cast<const int32_t*>(q_lens);
     return attention_bwd(t, B, H, Sq, Sk, D, scale, causal, S(st), F(ws));
   }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("dout"), py::arg("dq"), py::arg("dk"),
         py::arg("dv"), py::arg("lse"), py::arg("delta"), py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"), py::arg("dbq") = 0, py::arg("dbk") = 0,
         py::arg("dbv") = 0, py::arg("db_ld") = 0, py::arg("ws") = 0, py::arg("drop_t") = 0, py::arg("seed") = 0,
-        py::arg("seed_dev") = 0, py::arg("kv_lens") = 0);
+        py::arg("seed_dev") = 0, py::arg("kv_lens") = 0, py::arg("q_lens") = 0);
   m.def("attention_bwd_workspace", &attention_bwd_workspace, py::arg("B"), py::arg("H"), py::arg("Sq"),
         py::arg("Sk"), py::arg("D"), py::arg("causal"), py::arg("dbias"), py::arg("varlen") = false);
   m.def("gemm", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre, int M, int N, int K,

@@ -108,11 +108,18 @@ struct AttnTensors {
   // call without lengths).  With lengths the backward is always the dQ +
   // dK/dV kernel pair.
   const int32_t* kv_lens = nullptr;
+  // per-sample query lengths: int32 [B] on the device, clamped to [0, Sq], with
+  // or without kv_lens.  Queries >= q_lens[b] of sample b do not exist: their
+  // Q / O / dO / lse rows are never read, o = 0, lse = -inf and dQ = 0 are
+  // written for them, and they add nothing to dK / dV.  Served by the kernels
+  // of a call with key lengths (always the dQ + dK/dV pair); nullptr = every
+  // sample has Sq queries.
+  const int32_t* q_lens = nullptr;
 };
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st);
 // Returns the path that ran: 1 = the one-pass kernel (D = 64, non-causal,
-// Sk <= 512, no dbias, no dropout, no key lengths; FFK_ATTN_BWD_ONEPASS=0 turns
+// Sk <= 512, no dbias, no dropout, no key or query lengths; FFK_ATTN_BWD_ONEPASS=0 turns
 // it off), 0 = the dQ and
 // dK/dV kernels.  With Sk > 256 the one-pass kernel needs `ws`, an fp32
 // scratch of attention_bwd_workspace() floats (0: the call is not eligible

@@ -540,17 +540,27 @@ class FFModel:
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
-                            seq_parallel_mode="auto", key_lengths=None):
+                            seq_parallel_mode="auto", key_lengths=None, query_lengths=False):
         """``seq_parallel_mode`` selects the lowering when a strategy shards
         the sequence dim: "ulysses" (all-to-all), "ring" or "auto".
 
         ``key_lengths``: optional ``DT_INT32`` tensor [batch] of per-sample
         key lengths (a padding mask): keys at or past ``key_lengths[b]`` do
-        not exist for sample b.  Not available on the sequence-parallel path."""
+        not exist for sample b.  Not available on the sequence-parallel path.
+
+        ``query_lengths=True``: ``key_lengths`` also gives each sample's query
+        length (self-attention over a padded batch; query and key sequence
+        extents must be equal).  Queries at or past it do not exist: the
+        attention output there is the output bias, and the kernels skip them.
+        Exact for training when the loss ignores the padded positions."""
         inputs, extra = [query, key, value], {}
+        if query_lengths and key_lengths is None:
+            raise ValueError("multihead_attention: query_lengths=True needs key_lengths (the tensor bounds both axes)")
         if key_lengths is not None:
             inputs.append(key_lengths)
             extra["key_lengths"] = True
+            if query_lengths:
+                extra["query_lengths"] = True
         return self._add("MULTIHEAD_ATTENTION", inputs, name, (kernel_initializer,),
                          embed_dim=embed_dim, num_heads=num_heads, kdim=kdim, vdim=vdim, dropout=float(dropout),
                          bias=bias, add_bias_kv=add_bias_kv, add_zero_attn=add_zero_attn, causal=causal,

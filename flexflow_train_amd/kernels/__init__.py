@@ -438,7 +438,26 @@ def _attn_kv_lens(kv_lens, q):
     return kv_lens.data_ptr()
 
 
-def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None):
+def _attn_q_lens(q_lens, q):
+    """Pointer of an attention call's per-sample query lengths (0: none),
+    checked like the key lengths: metadata only, the kernels read the values
+    and clamp them to [0, Sq]."""
+    if q_lens is None:
+        return 0
+    if not isinstance(q_lens, torch.Tensor) or q_lens.dtype != torch.int32:
+        raise ValueError("attention: q_lens must be an int32 tensor")
+    if tuple(q_lens.shape) != (q.shape[0],):
+        raise ValueError(f"attention: q_lens has shape {tuple(q_lens.shape)}, expected ({q.shape[0]},)")
+    if q_lens.device != q.device:
+        raise ValueError("attention: q_lens must be on the device of q")
+    if not q_lens.is_contiguous():
+        raise ValueError("attention: q_lens must be contiguous")
+    STATS["attention_qlens"] += 1
+    return q_lens.data_ptr()
+
+
+def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None,
+                  q_lens=None):
     """Flash attention forward.  q,k,v: [B, S, H, D] bf16 views (any b/s/h
     strides, e.g. slices of a packed [B, S, 3, H, D] QKV buffer).
     Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain).
@@ -454,7 +473,13 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     get probability 0 and their K / V rows are never read, so padding content
     (NaN included) cannot reach the output.  A row with no live key gives
     o = 0 and lse = -inf.  The kernels read the tensor, so a captured call
-    follows it."""
+    follows it.
+
+    ``q_lens``: optional int32 [B] device tensor of per-sample query lengths,
+    0 <= q_lens[b] <= Sq, with or without ``kv_lens``.  Queries >= q_lens[b] of
+    sample b do not exist: their Q rows are never read, they are skipped in
+    the kernels (whole 128-row blocks and 32-row waves do no attention work)
+    and o = 0, lse = -inf are stored for them."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     if D not in (64, 128):
@@ -463,24 +488,27 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
         raise ValueError("attention: q/k/v shape mismatch")
     drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
     lens = _attn_kv_lens(kv_lens, q)
+    qlens = _attn_q_lens(q_lens, q)
     if out is None:
         out = torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
     lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
     sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     ext().attention_fwd(_view4(q), _view4(k), _view4(v), _view4(out), lse.data_ptr(), B, H, Sq, Sk, D, sc,
-                        bool(causal), _stream(), *drop, lens)
+                        bool(causal), _stream(), *drop, lens, **({"q_lens": qlens} if qlens else {}))
     STATS["attention_fwd"] += 1
     return out, lse
 
 
 def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False,
-                  dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None):
+                  dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None, q_lens=None):
     """Flash-attention backward into dq / dk / dv; returns the path that ran
     (1: the one-pass kernel, 0: the dQ and dK/dV kernels).  ``dropout_p``,
     ``seed``, ``seed_dev``: those of the forward call that produced ``o``
     (dropout always takes path 0).  ``kv_lens``: the forward call's key
     lengths (always path 0); dk / dv rows past a sample's length are written
-    as zeros.  ``dbias`` = optional
+    as zeros.  ``q_lens``: the forward call's query lengths (always path 0);
+    dq rows past a sample's length are written as zeros, they add nothing to
+    dk / dv, and their q / o / do / lse rows are never read.  ``dbias`` = optional
     (dbq, dbk, dbv) fp32 [H*D] projection-bias gradients, accumulated with the
     column sums of dq / dk / dv (over batch and sequence) computed in the
     kernels' epilogues: by default each wave stores its 32-row partial into a
@@ -513,12 +541,13 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     # first key block's dQ in an fp32 scratch when there is a second one
     drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
     lens = _attn_kv_lens(kv_lens, q)
+    qlens = _attn_q_lens(q_lens, q)
     n_ws = 0 if drop[0] else ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal), dbias is not None,
-                                                            bool(lens))
+                                                            bool(lens or qlens))
     ws = torch.empty(n_ws, device=q.device, dtype=torch.float32) if n_ws else None
     path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
                                _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
-                               _stream(), *dbs, ld, _p(ws), *drop, lens)
+                               _stream(), *dbs, ld, _p(ws), *drop, lens, **({"q_lens": qlens} if qlens else {}))
     if path == 1:
         STATS["attention_bwd_onepass"] += 1
     if slab is not None:

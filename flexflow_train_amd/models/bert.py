@@ -43,6 +43,10 @@ class BertConfig:
     # True: an int32 input `seq_lens` [batch] carries every sample's true
     # length; keys at or past it do not exist for any layer's attention
     key_lengths: bool = False
+    # True (needs key_lengths): positions at or past a sample's length do not
+    # exist as queries either; every layer's attention skips them.  For
+    # training with a loss that ignores the padded positions
+    query_lengths: bool = False
 
     @property
     def padded_vocab(self) -> int:
@@ -84,6 +88,8 @@ def build_bert(model: FFModel, cfg: BertConfig) -> Tuple[Dict[str, object], obje
         x = model.create_tensor([B, S, E], DataType.DT_FLOAT, create_grad=True, name="hidden_input")
         inputs["hidden_input"] = x
     lens = None
+    if cfg.query_lengths and not cfg.key_lengths:
+        raise ValueError("BertConfig: query_lengths=True requires key_lengths=True")
     if cfg.key_lengths:
         lens = model.create_tensor([B], DataType.DT_INT32, create_grad=False, name="seq_lens")
         inputs["seq_lens"] = lens
@@ -91,7 +97,8 @@ def build_bert(model: FFModel, cfg: BertConfig) -> Tuple[Dict[str, object], obje
     for i in range(cfg.num_encoder_layers):
         pre = f"encoder.{i}"
         a = model.multihead_attention(x, x, x, E, cfg.num_heads, dropout=cfg.attention_probs_dropout_prob,
-                                      bias=True, kernel_initializer=proj_init, name=f"{pre}.attn", key_lengths=lens)
+                                      bias=True, kernel_initializer=proj_init, name=f"{pre}.attn", key_lengths=lens,
+                                      query_lengths=cfg.query_lengths)
         if cfg.hidden_dropout_prob > 0:
             a = model.dropout(a, cfg.hidden_dropout_prob, i, name=f"{pre}.attn_dropout")
         x = model.layer_norm(model.add(a, x, name=f"{pre}.attn_residual"), [-1], True, cfg.layer_norm_eps,

@@ -23,6 +23,13 @@ rows are never read, so padding content (NaN included) cannot reach an output;
 a row without a live key gives o = 0 and dQ = 0.  The flash kernels read the
 lengths from the device tensor (a captured step follows a new batch's lengths);
 the torch fallback applies the same definition as a mask.
+
+Query lengths (attribute ``query_lengths``): the fourth input also gives each
+sample's query length, for self-attention over a padded batch.  Queries >=
+lens[b] do not exist: their rows of q and of the incoming gradient are never
+read, o = 0 and dQ = 0 there, and they add nothing to dK / dV.  The kernels
+skip them, so the attention work of a sample follows lens[b]^2.  Exact when
+the loss ignores the padded positions (their incoming gradient is zero).
 """
 from __future__ import annotations
 
@@ -82,11 +89,17 @@ def _split_weights(W, E, Hl, kd, vd, Eq, Ek, Ev):
     return {"q": Wq, "k": Wk, "v": Wv, "o": Wo}
 
 
-def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None):
+def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=None):
     # q,k,v: [B, S, H, D] -> [B, S, H, D]; drop = (keep mask [B, H, Sq, Sk], keep scale)
-    # kv_lens: [B] integer key lengths (module docstring)
+    # kv_lens, q_lens: [B] integer key / query lengths (module docstring)
     qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
-    dead = None
+    dead = qdead = None
+    if q_lens is not None:
+        Sq = q.shape[1]
+        qdead = torch.arange(Sq, device=q.device).view(1, Sq) >= q_lens.view(-1, 1).clamp(0, Sq)  # [B, Sq]
+        # dead Q rows are never read: zeros in their place; the fill of the
+        # output below does the same to the incoming gradient's dead rows
+        qt = qt.masked_fill(qdead[:, None, :, None], 0)
     if kv_lens is not None:
         Sk = k.shape[1]
         dead = torch.arange(Sk, device=k.device).view(1, Sk) >= kv_lens.view(-1, 1).clamp(0, Sk)  # [B, Sk]
@@ -108,7 +121,10 @@ def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None):
         p = p.masked_fill(dead[:, None, None, :], 0.0)
     if drop is not None:
         p = p * drop[0].to(p.dtype) * drop[1]
-    return torch.matmul(p, vt.float()).transpose(1, 2).to(q.dtype)
+    o = torch.matmul(p, vt.float())
+    if qdead is not None:
+        o = o.masked_fill(qdead[:, None, :, None], 0)
+    return o.transpose(1, 2).to(q.dtype)
 
 
 _M32 = 0xFFFFFFFF
@@ -302,6 +318,12 @@ class MultiHeadAttentionOp(OpImpl):
                 raise ValueError(f"{ctx.name}: key lengths must be an integer tensor [batch], got "
                                  f"{lens.dtype} {tuple(inputs[3].shape)}")
             lens = lens.to(torch.int32).contiguous()
+        # query_lengths: the same tensor bounds the query axis (self-attention over a padded batch)
+        qlens = None
+        if bool(ctx.a("query_lengths", False)):
+            if lens is None:
+                raise ValueError(f"{ctx.name}: query_lengths needs the key lengths input")
+            qlens = lens
         W = weights[0]
         b_in = weights[1] if len(weights) > 1 else None
         b_out = weights[2] if len(weights) > 2 and ctx.sum_index == 0 else None
@@ -338,6 +360,9 @@ class MultiHeadAttentionOp(OpImpl):
             if lens is not None:
                 raise NotImplementedError(f"{ctx.name}: key lengths are not supported on the sequence-parallel "
                                           "(ring / Ulysses) attention path")
+            if qlens is not None:
+                raise NotImplementedError(f"{ctx.name}: query lengths are not supported on the sequence-parallel "
+                                          "(ring / Ulysses) attention path")
             if p_drop > 0 and not ctx.extra.get("attn_drop_warned"):
                 ctx.extra["attn_drop_warned"] = True
                 warnings.warn(f"{ctx.name}: attention dropout is not applied on the sequence-parallel path")
@@ -349,17 +374,18 @@ class MultiHeadAttentionOp(OpImpl):
                 drop = (p_drop, _drop_seed(ctx), _drop_step(ctx, q.device))
             if use_flash:
                 kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
-                o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale, kv_lens=lens, **kw)
+                o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale, kv_lens=lens, q_lens=qlens, **kw)
             else:
-                o, lse = _torch_attention(q, k, v, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens), None
+                o, lse = _torch_attention(q, k, v, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens,
+                                          qlens), None
         o2 = o.reshape(B * Sq, Hl * vd)
         out = matmul(o2, ws["o"], bias=b_out)
         saved = (x2, k_in if not self_attn else None, v_in if not self_attn else None, proj, o, lse, ws,
-                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale), lens, drop)
+                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale), (lens, qlens), drop)
         return [out.view(B, Sq, E)], saved
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
-        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims, lens, drop = saved
+        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims, (lens, qlens), drop = saved
         no_lens_grad = [None] if lens is not None else []   # the lengths input gets no gradient
         B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale = dims
         dW = weight_grads[0]
@@ -413,12 +439,12 @@ class MultiHeadAttentionOp(OpImpl):
                 fused_db = (dbf[:n], dbf[n:2 * n], dbf[2 * n:3 * n])
             kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
             K.attention_bwd(q, k, v, o, lse, do4, dq, dk, dv, causal=causal, scale=scale, dbias=fused_db,
-                            kv_lens=lens, **kw)
+                            kv_lens=lens, q_lens=qlens, **kw)
             if fused_db is not None:
                 db_in = None   # accumulated by the attention backward kernels
         else:
             qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-            ref = _torch_attention(qf, kf, vf, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens)
+            ref = _torch_attention(qf, kf, vf, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens, qlens)
             ref.float().backward(do4.float())
             dq, dk, dv = (t.grad.to(do.dtype) for t in (qf, kf, vf))
             if self_attn:

@@ -7,6 +7,7 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
     python tools/attn_time.py --pipe-ab | --delta-ab | --onepass-ab   (same-process A/B of a kernel switch)
     python tools/attn_time.py --dropout 0.1                           (attention dropout against p = 0)
     python tools/attn_time.py --varlen [--dropout 0.1]                (per-sample key lengths against full length)
+    python tools/attn_time.py --varlen --queries [--dropout 0.1]      (the same lengths as query lengths too)
 """
 import json
 import os
@@ -123,7 +124,7 @@ def dropout_ab(p, iters, rounds=5):
         print(json.dumps(rec), flush=True)
 
 
-def varlen_ab(iters, rounds=5, seed=0, p=0.0):
+def varlen_ab(iters, rounds=5, seed=0, p=0.0, queries=False):
     """Interleaved same-process timing of the forward and the backward with
     per-sample key lengths drawn uniformly from [Sk / 8, Sk] (fixed seed)
     against the same call without lengths, and against lengths all equal to
@@ -133,7 +134,11 @@ def varlen_ab(iters, rounds=5, seed=0, p=0.0):
     against "none" is then the cost of the forms with lengths and dropout,
     whose dQ kernel takes delta from the probabilities.  `live_tiles` is
     the fraction of 64-key tiles with a live key (the causal shapes count the
-    tiles at or below the diagonal of each 128-query block only)."""
+    tiles at or below the diagonal of each 128-query block only).
+    `queries` adds a fourth variant, "varlen_q": the same lengths as the query
+    lengths too (self-attention over a padded batch).  `live_pairs_q` is its
+    share of live (128-query block, 64-key tile) pairs: of the pairs counted
+    by `live_tiles`, those whose block also has a live query."""
     import statistics
     for name, (B, S, H, D, causal) in SHAPES.items():
         g = torch.Generator(device="cuda").manual_seed(0)
@@ -144,16 +149,22 @@ def varlen_ab(iters, rounds=5, seed=0, p=0.0):
         lens_cpu = torch.randint(S // 8, S + 1, (B,), generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
         variants = {"none": None, "full": torch.full((B,), S, device="cuda", dtype=torch.int32),
                     "varlen": lens_cpu.cuda()}
-        live = total = 0
+        if queries:
+            variants["varlen_q"] = variants["varlen"]
+        live = live_q = total = 0
         for n in lens_cpu.tolist():
             for qb in range((S + 127) // 128):
                 cap = min((S + 63) // 64, (qb * 128 + 128 + 63) // 64) if causal else (S + 63) // 64
                 total += cap
                 live += min(cap, (n + 63) // 64)
+                if qb * 128 < n:
+                    live_q += min(cap, (n + 63) // 64)
         t = {}
         for _ in range(rounds):
             for tag, lens in variants.items():
                 kw = dict(causal=causal, kv_lens=lens, dropout_p=p, seed=1234)
+                if tag == "varlen_q":
+                    kw["q_lens"] = lens
                 o, lse = K.attention_fwd(q, k, v, **kw)
                 t.setdefault(("fwd", tag), []).append(_time(lambda: K.attention_fwd(q, k, v, out=o, **kw), iters))
                 t.setdefault(("bwd", tag), []).append(_time(
@@ -162,6 +173,8 @@ def varlen_ab(iters, rounds=5, seed=0, p=0.0):
         med = {key: statistics.median(x) for key, x in t.items()}
         rec = {"shape": name, "seed": seed, "dropout": p, "mean_len": round(float(lens_cpu.float().mean()), 1),
                "live_tiles": round(live / total, 4)}
+        if queries:
+            rec["live_pairs_q"] = round(live_q / total, 4)
         for which in ("fwd", "bwd"):
             for tag in variants:
                 rec[f"{which}_ms_{tag}"] = round(med[(which, tag)], 4)
@@ -171,7 +184,8 @@ def varlen_ab(iters, rounds=5, seed=0, p=0.0):
 
 def main():
     if "--varlen" in sys.argv:         # per-sample key lengths against full length
-        return varlen_ab(30, p=float(sys.argv[sys.argv.index("--dropout") + 1]) if "--dropout" in sys.argv else 0.0)
+        return varlen_ab(30, p=float(sys.argv[sys.argv.index("--dropout") + 1]) if "--dropout" in sys.argv else 0.0,
+                         queries="--queries" in sys.argv)
     if "--dropout" in sys.argv:        # attention dropout against p = 0, forward and backward
         return dropout_ab(float(sys.argv[sys.argv.index("--dropout") + 1]), 30)
     if "--pmc-run" in sys.argv:
