@@ -6,7 +6,7 @@
 // matrix never leaves the CU (blockwise online softmax), which is what makes
 // the long-sequence configs of SURVEY.md §5.7 possible.
 //
-// CDNA4 design (see /opt/skills/guides/cdna_hip_programming.md §3, §5.5):
+// CDNA4 design:
 //  * MFMA v_mfma_f32_32x32x16_bf16; a workgroup = 4 waves, each wave owns 32
 //    query rows (forward, dQ) or 32 key rows (dK/dV).
 //  * "swapped" products: the forward computes S^T = K Q^T so every lane holds
@@ -21,6 +21,8 @@
 //  * LDS images are XOR-swizzled per row so ds_read_b128 row reads are
 //    conflict-free; V^T (and K^T / Q^T / dO^T in the backward) operands come
 //    from ds_read_b64_tr_b16 hardware-transposed reads of the same images.
+//  * output rows leave as 16-byte stores (store_rows16), and non-causal grids
+//    visit the heads in XCD-local order (attn_head_block).
 //  * backward = dQ kernel (query block resident; also computes delta =
 //    rowsum(dO*O) for its queries) then dK/dV kernel (key block resident,
 //    loops over query tiles, key on the lane) -> no float atomics,
@@ -28,9 +30,17 @@
 //    512 keys take the one-pass kernel instead (attn_bwd_onepass_kernel): one
 //    workgroup per (batch, head), all three gradients from one S / dS.
 //
+// Kernels: attn_fwd_kernel, attn_bwd_dq_kernel and attn_bwd_dkdv_kernel, each
+// for D in {64, 128} x CAUSAL x DROP x VARLEN, and attn_bwd_onepass_kernel;
+// attention_fwd / attention_bwd pick one through with_head and with_features.
+// Two environment switches: FFK_ATTN_PRIO (wave priority around the MFMA
+// clusters; default on at D = 128) and FFK_ATTN_BWD_ONEPASS (0: the kernel
+// pair where the one-pass kernel would run; read per call).
+//
 // Tensor addressing: every tensor is [B, S, H, D] with arbitrary strides for
-// b / s / h and contiguous d, so the fused QKV projection output
-// [B, S, 3, H, D] is consumed in place.  LSE is [B, H, S] fp32, log2 domain.
+// b / s / h and contiguous d (TensorViewT::row), so the fused QKV projection
+// output [B, S, 3, H, D] is consumed in place.  LSE is [B, H, S] fp32, log2
+// domain.
 //
 // Attention dropout (DROP instantiations of the forward, dQ and dK/dV
 // kernels).  The keep / drop decision of probability (b, h, q, k) is a pure
@@ -81,22 +91,26 @@
 // kernel: null means the physical extent.  The dropout hash index and the
 // dbias slab rows keep their physical positions.
 #include <cstdlib>
+#include <type_traits>
 
 #include "kernels.h"
 #include "mfma.h"
 
 namespace ffk {
 
-struct TensorView {
-  const bf16* p;
-  int64_t sb, ss, sh;  // element strides; d is contiguous
+// A [B, S, H, D] tensor: element strides for b / s / h, d contiguous.
+template <class T>
+struct TensorViewT {
+  T* p;
+  int64_t sb, ss, sh;
+  __device__ __forceinline__ T* row(int b, int s, int h) const { return p + b * sb + static_cast<int64_t>(s) * ss + h * sh; }
 };
+using TensorView = TensorViewT<const bf16>;
+using OutView = TensorViewT<bf16>;
 
 struct AttnParams {
   TensorView q, k, v, o, dout;
-  bf16 *o_out, *dq, *dk, *dv;
-  int64_t o_sb, o_ss, o_sh;                   // output strides (o_out)
-  int64_t dq_sb, dq_ss, dq_sh, dk_sb, dk_ss, dk_sh, dv_sb, dv_ss, dv_sh;
+  OutView o_out, dq, dk, dv;
   float* lse;    // [B, H, Sq] log2-domain
   float* delta;  // [B, H, Sq]
   float *dbq, *dbk, *dbv;  // optional [H*D] projection-bias gradients (column sums of dq / dk / dv)
@@ -106,17 +120,19 @@ struct AttnParams {
   float scale_log2;  // scale * log2(e)
   float inv_scale_log2;  // 1 / scale_log2 (no IEEE divide in the loops)
   int prio;          // raise wave priority around MFMA clusters (FFK_ATTN_PRIO; guide T5)
-  int xcd;           // XCD-local head order of non-causal grids (FFK_ATTN_XCD, default on)
-  int wide_store;    // 16-B output rows via permlane32_swap (FFK_ATTN_WIDE_STORE, default on)
-  // attention dropout (DROP kernels only; appended so the other fields keep their offsets)
+  // attention dropout (DROP kernels only)
   unsigned drop_thr;        // T << 8: a probability is dropped iff its hash word is below this
   float drop_rs;            // keep scale 2^24 / (2^24 - T)
   uint64_t seed;
   const int64_t* seed_dev;  // optional device-resident addend of the seed
-  // per-sample key lengths (VARLEN kernels only; appended like the dropout fields)
+  // per-sample lengths (VARLEN kernels only)
   const int32_t* kv_lens;   // [B]; keys >= kv_lens[b] of sample b do not exist
   const int32_t* q_lens;    // [B]; queries >= q_lens[b] of sample b do not exist
 };
+
+// Row of register r of a 32 x 32 MFMA accumulator, before the lane half's
+// + 4 h: registers 4g .. 4g+3 hold rows 8g .. 8g+3.
+__device__ constexpr int acc_row(int r) { return (r & 3) + 8 * (r >> 2); }
 
 // Key-axis bound of sample b.  VARLEN: the sample's own length, read from the
 // device (so a captured launch follows the tensor) and clamped to [0, Sk] so
@@ -200,12 +216,7 @@ __device__ __forceinline__ void store_rows16(bf16* row, const f32x16 (&acc)[DT],
 // XCD's L2 fetches that head's K / V.  The bijective remap (mfma.h) gives
 // each XCD a contiguous range of linear ids, i.e. whole heads: a head's K / V
 // come from HBM once and its other blocks hit in the XCD's L2.
-__device__ __forceinline__ void attn_head_block(const AttnParams& P, int& bh, int& blk) {
-  if (!P.xcd) {
-    bh = blockIdx.y;
-    blk = blockIdx.x;
-    return;
-  }
+__device__ __forceinline__ void attn_head_block(int& bh, int& blk) {
   const int W = gridDim.x * gridDim.y;
   const int r = xcd_remap(blockIdx.x + blockIdx.y * gridDim.x, W);
   bh = r / gridDim.x;
@@ -243,7 +254,7 @@ __device__ __forceinline__ void bias_colsum(const f32x16 (&acc)[DT], float mul, 
       float v = acc[dt][r];
 #pragma unroll
       for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-      if ((lane & 31) == 0) atomicAdd(db + dt * 32 + 8 * (r >> 2) + 4 * h + (r & 3), v * mul);
+      if ((lane & 31) == 0) atomicAdd(db + dt * 32 + acc_row(r) + 4 * h, v * mul);
     }
 }
 
@@ -259,8 +270,7 @@ struct TileLoader {
       const int c = threadIdx.x + NT * i;
       const int r = c / (D / 8), ch = c % (D / 8);
       if (row0 + r < nrows) {
-        reg[i] = *reinterpret_cast<const bf16x8*>(t.p + b * t.sb + static_cast<int64_t>(row0 + r) * t.ss +
-                                                  h * t.sh + ch * 8);
+        reg[i] = *reinterpret_cast<const bf16x8*>(t.row(b, row0 + r, h) + ch * 8);
       } else {
         reg[i] = bf16x8{};
       }
@@ -314,7 +324,7 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 #pragma unroll
   for (int t = 0; t < NV / 32; ++t) {
     const int k = (lane & 31) * (NV / 32) + t, dt = k >> 4, r = k & 15;
-    row[dt * 32 + 8 * (r >> 2) + 4 * h + (r & 3)] = v[t] * mul;
+    row[dt * 32 + acc_row(r) + 4 * h] = v[t] * mul;
   }
 }
 
@@ -323,7 +333,7 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 // DROP: the dropped probabilities are zeroed after the row sum is taken, so
 // m, l and the LSE are those of the undropped softmax; the keep scale is
 // folded into the epilogue's 1 / l.
-template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   constexpr int KS = D / 16;        // k-steps over the head dim
   constexpr int DT = D / 32;        // 32-wide output tiles over the head dim
@@ -336,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   // head dispatched first — longest-first order, so the kernel's tail is the
   // light blocks near the sequence start
   int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;
-  if (!CAUSAL) attn_head_block(P, bh, qb);
+  if (!CAUSAL) attn_head_block(bh, qb);
   const int b = bh / P.H, hh = bh % P.H;
   const int q_blk = qb * 128;
   const int qw = q_blk + wave * 32;
@@ -349,7 +359,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   if constexpr (VARLEN) {
     if (q_blk >= Sql) {  // a wholly dead block: o = 0, lse = -inf, no tile loop
       if (q_ok) {
-        store_zero_rows<D>(P.o_out + b * P.o_sb + static_cast<int64_t>(q) * P.o_ss + hh * P.o_sh, h);
+        store_zero_rows<D>(P.o_out.row(b, q, hh), h);
         if (h == 0) P.lse[static_cast<int64_t>(bh) * P.Sq + q] = -INFINITY;
       }
       return;
@@ -360,15 +370,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   bf16x8 qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
-    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.p + b * P.q.sb + static_cast<int64_t>(q) * P.q.ss +
-                                                     hh * P.q.sh + ks * 16 + 8 * h)
-                  : bf16x8{};
+    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.row(b, q, hh) + ks * 16 + 8 * h) : bf16x8{};
 
   f32x16 o[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt) o[dt] = f32x16{};
   float m = -INFINITY, l = 0.f;
-  // dropout: hash index of s[kt][r] = drow + k0 + kt * 32 + (r & 3) + 8 * (r >> 2)
+  // dropout: hash index of s[kt][r] = drow + k0 + kt * 32 + acc_row(r)
   [[maybe_unused]] unsigned dkey = 0, drow = 0;
   if constexpr (DROP) {
     dkey = drop_key(P, bh);
@@ -436,7 +444,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int key = k0 + kt * 32 + acc_row(r) + 4 * h;
             if (key >= Skl || (CAUSAL && key > q)) s[kt][r] = -INFINITY;
           }
       }
@@ -480,7 +488,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (dropped(dt0 + (kt * 32 + (r & 3) + 8 * (r >> 2)), dkey, P.drop_thr)) s[kt][r] = 0.f;
+            if (dropped(dt0 + (kt * 32 + acc_row(r)), dkey, P.drop_thr)) s[kt][r] = 0.f;
       }
       // ---- O^T[d][q] += V^T[d][key] P^T[key][q]
       prio_hi(P);
@@ -517,203 +525,15 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   }
   float inv = lt > 0.f ? 1.f / lt : 0.f;
   if constexpr (DROP) inv *= P.drop_rs;
-  bf16* orow = P.o_out + b * P.o_sb + static_cast<int64_t>(q) * P.o_ss + hh * P.o_sh;
-  if (P.wide_store) {
-    store_rows16<DT>(orow, o, inv, h, q_ok);
-  } else if (q_ok) {
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        bf16x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = f2bf(o[dt][4 * g4 + e] * inv);
-        *reinterpret_cast<bf16x4*>(orow + dt * 32 + 8 * g4 + 4 * h) = v;
-      }
-  }
+  store_rows16<DT>(P.o_out.row(b, q, hh), o, inv, h, q_ok);
+  // VARLEN: the LSE index is formed here from an opaque copy of the row.  The
+  // dead-block exit above forms the same 64-bit index, and as one value it
+  // was hoisted above the tile loop and spilled across it (non-causal D = 128
+  // with dropout, 256 registers: 20 bytes of scratch and a reload in the loop)
+  int ql = q;
+  if constexpr (VARLEN) asm volatile("" : "+v"(ql));
   if (q_ok && h == 0)
-    P.lse[static_cast<int64_t>(bh) * P.Sq + q] = (lt > 0.f) ? m * P.scale_log2 + log2f(lt) : -INFINITY;
-}
-
-// ===========================================================================
-// Forward, software-pipelined across K/V tiles (FFK_ATTN_FWD_PIPE=1): the
-// scores of tile t+1 (S MFMAs) are computed while tile t's softmax runs on
-// the VALU, and tile t's P.V MFMAs follow, so inside ONE wave the matrix cores
-// and the VALU work on different tiles instead of waiting for each other
-// (guide "sm-split"; with one barrier per tile the two waves of a SIMD run in
-// phase, so the overlap has to come from within the wave).  K leads V by one
-// tile in the LDS ring: during iteration t a buffer holds {K(t+1), V(t)}.
-template <int D, bool CAUSAL>
-__global__ __launch_bounds__(256, 2) void attn_fwd_pipe_kernel(AttnParams P) {
-  constexpr int KS = D / 16, DT = D / 32, KV = 64;
-  constexpr int TILE_BYTES = KV * D * 2;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[4 * TILE_BYTES];  // [K V] x 2
-
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
-  int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;
-  if (!CAUSAL) attn_head_block(P, bh, qb);
-  const int b = bh / P.H, hh = bh % P.H;
-  const int q_blk = qb * 128;
-  const int qw = q_blk + wave * 32;
-  const int q = qw + (lane & 31);
-  const bool q_ok = q < P.Sq;
-
-  bf16x8 qf[KS];
-#pragma unroll
-  for (int ks = 0; ks < KS; ++ks)
-    qf[ks] = q_ok ? *reinterpret_cast<const bf16x8*>(P.q.p + b * P.q.sb + static_cast<int64_t>(q) * P.q.ss +
-                                                     hh * P.q.sh + ks * 16 + 8 * h)
-                  : bf16x8{};
-
-  f32x16 o[DT];
-#pragma unroll
-  for (int dt = 0; dt < DT; ++dt) o[dt] = f32x16{};
-  float m = -INFINITY, l = 0.f;
-
-  int n_tiles = (P.Sk + KV - 1) / KV;
-  if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
-  auto active = [&](int t) { return t < n_tiles && (!CAUSAL || t * KV <= qw + 31); };
-
-  auto scores = [&](const unsigned char* Kt, f32x16 (&s)[2]) {
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-      s[kt] = f32x16{};
-#pragma unroll
-      for (int ks = 0; ks < KS; ++ks)
-        s[kt] = mfma32(lds_read16(Kt, lds_off<D>(kt * 32 + (lane & 31), 2 * ks + h)), qf[ks], s[kt]);
-    }
-  };
-
-  TileLoader<D, KV> kl, vl;
-  // prologue: K(0) -> buffer 1's K slot (free until iteration 0 ends), K(1) and
-  // V(0) -> buffer 0
-  kl.load(P.k, b, hh, 0, P.Sk);
-  kl.store(smem + 2 * TILE_BYTES);
-  if (n_tiles > 1) kl.load(P.k, b, hh, KV, P.Sk);
-  vl.load(P.v, b, hh, 0, P.Sk);
-  if (n_tiles > 1) kl.store(smem);
-  vl.store(smem + TILE_BYTES);
-  __syncthreads();
-  f32x16 sa[2], sb[2];
-  if (active(0)) scores(smem + 2 * TILE_BYTES, sa);
-  __syncthreads();   // every wave read K(0) before iteration 0 restages buffer 1
-
-  // one tile: softmax(t) on `sc` (+ S(t+1) into `sn` from the current buffer),
-  // then O += V(t)^T P(t)
-  auto step = [&](int t, f32x16 (&sc)[2], f32x16 (&sn)[2]) {
-    const int k0 = t * KV;
-    const unsigned char* buf = smem + (t & 1) * 2 * TILE_BYTES;
-    const unsigned char* Kn = buf;                 // K(t+1)
-    const unsigned char* Vt = buf + TILE_BYTES;    // V(t)
-    const bool more_k = t + 2 < n_tiles, more_v = t + 1 < n_tiles;
-    if (more_k) kl.load(P.k, b, hh, k0 + 2 * KV, P.Sk);
-    if (more_v) vl.load(P.v, b, hh, k0 + KV, P.Sk);
-    const bool act = active(t);
-    // S(t+1): independent of this tile's softmax — the scheduler interleaves
-    // its MFMAs with the VALU work below
-    if (active(t + 1)) scores(Kn, sn);
-    if (act) {
-      const bool need_mask = (k0 + KV > P.Sk) || (CAUSAL && k0 + KV - 1 > qw);
-      if (need_mask) {
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (key >= P.Sk || (CAUSAL && key > q)) sc[kt][r] = -INFINITY;
-          }
-      }
-      float t0 = fmax3(sc[0][0], sc[0][1], sc[0][2]);
-      float t1 = fmax3(sc[1][0], sc[1][1], sc[1][2]);
-#pragma unroll
-      for (int r = 3; r < 15; r += 2) {
-        t0 = fmax3(t0, sc[0][r], sc[0][r + 1]);
-        t1 = fmax3(t1, sc[1][r], sc[1][r + 1]);
-      }
-      float tmax = fmax3(fmax3(t0, sc[0][15], sc[1][15]), t1, t1);
-      const float tother = __shfl_xor(tmax, 32, 64);
-      tmax = fmax3(tmax, tother, tother);
-      if (__any(tmax > m + 8.f * P.inv_scale_log2)) {
-        const float m_new = fmaxf(m, tmax);
-        const float alpha = (m_new == -INFINITY) ? 1.f : fexp2((m - m_new) * P.scale_log2);
-        m = m_new;
-        l *= alpha;
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt) o[dt] *= alpha;
-      }
-      const float mc = (m == -INFINITY) ? 0.f : m * P.scale_log2;
-      float psum[2] = {0.f, 0.f};
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const float pv = fexp2(fmaf(sc[kt][r], P.scale_log2, -mc));
-          sc[kt][r] = pv;
-          psum[kt] += pv;
-        }
-      l += psum[0] + psum[1];
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-          const bf16x8 pf = acc_to_frag(sc[kt], st);
-#pragma unroll
-          for (int dt = 0; dt < DT; ++dt) o[dt] = mfma32(tr_frag<D>(Vt, kt * 32 + 16 * st, dt, lane), pf, o[dt]);
-        }
-    }
-    unsigned char* nb = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
-    if (more_k) kl.store(nb);
-    if (more_v) vl.store(nb + TILE_BYTES);
-    __syncthreads();
-  };
-
-  int t = 0;
-  for (; t + 1 < n_tiles; t += 2) {
-    step(t, sa, sb);
-    step(t + 1, sb, sa);
-  }
-  if (t < n_tiles) step(t, sa, sb);
-
-  const float lt = l + __shfl_xor(l, 32, 64);
-  const float inv = lt > 0.f ? 1.f / lt : 0.f;
-  if (q_ok) {
-    bf16* orow = P.o_out + b * P.o_sb + static_cast<int64_t>(q) * P.o_ss + hh * P.o_sh;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        bf16x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = f2bf(o[dt][4 * g4 + e] * inv);
-        *reinterpret_cast<bf16x4*>(orow + dt * 32 + 8 * g4 + 4 * h) = v;
-      }
-    if (h == 0) P.lse[static_cast<int64_t>(bh) * P.Sq + q] = (lt > 0.f) ? m * P.scale_log2 + log2f(lt) : -INFINITY;
-  }
-}
-
-// ===========================================================================
-// Backward preprocessing: delta[b,h,q] = sum_d dO[q][d] * O[q][d]
-template <int D>
-__global__ __launch_bounds__(256) void attn_bwd_delta_kernel(AttnParams P) {
-  constexpr int TPR = D / 8;  // threads per row
-  const int64_t rows = static_cast<int64_t>(P.B) * P.H * P.Sq;
-  const int64_t row = (static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x) / TPR;
-  const int c = threadIdx.x % TPR;
-  float acc = 0.f;
-  if (row < rows) {
-    const int q = static_cast<int>(row % P.Sq);
-    const int bh = static_cast<int>(row / P.Sq);
-    const int b = bh / P.H, hh = bh % P.H;
-    u16x8 a = *reinterpret_cast<const u16x8*>(P.o.p + b * P.o.sb + static_cast<int64_t>(q) * P.o.ss +
-                                              hh * P.o.sh + c * 8);
-    u16x8 d = *reinterpret_cast<const u16x8*>(P.dout.p + b * P.dout.sb + static_cast<int64_t>(q) * P.dout.ss +
-                                              hh * P.dout.sh + c * 8);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) acc += u2f(a[k]) * u2f(d[k]);
-  }
-#pragma unroll
-  for (int o = TPR / 2; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-  if (row < rows && c == 0) P.delta[row] = acc;
+    P.lse[static_cast<int64_t>(bh) * P.Sq + ql] = (lt > 0.f) ? m * P.scale_log2 + log2f(lt) : -INFINITY;
 }
 
 // ===========================================================================
@@ -724,10 +544,10 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(AttnParams P) {
 // registers on top and spilled at 168 — a scratch reload inside the loop is a
 // VMEM op, and its vmcnt wait drained the next K / V tile's prefetch every
 // iteration — so the causal form runs 2 waves per SIMD without spills
-// FUSED_DELTA: delta = rowsum(dO * O) of the block's own queries is computed
-// here from the dO fragments already in registers (plus one 16-B O load per
-// fragment) and written out for the dK / dV kernel, which then runs AFTER
-// this one — the separate delta pass (a full re-read of dO and O) goes away.
+// delta = rowsum(dO * O) of the block's own queries is computed here from the
+// dO fragments already in registers (plus one 16-B O load per fragment) and
+// written out for the dK / dV kernel, which therefore runs AFTER this one;
+// there is no separate delta pass.
 // DROP: dS^T = P^T (keep rs dP^T - delta); same (lane -> query, register ->
 // key) coordinates as the forward.
 // VARLEN with DROP (XDELTA): delta is taken from the probabilities, delta =
@@ -741,16 +561,15 @@ __global__ __launch_bounds__(256) void attn_bwd_delta_kernel(AttnParams P) {
 // accumulates bq^T = K^T P^T from the K^T fragments of the dQ product (one
 // more MFMA product, DT more accumulators), and the epilogue adds
 // (dlt - delta) bq^T to dQ^T and writes delta for the dK / dV kernel.
-template <int D, bool CAUSAL, bool FUSED_DELTA = false, bool DROP = false, bool VARLEN = false>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN>
 __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, KV = 64;
   constexpr int TILE_BYTES = KV * D * 2;
   constexpr bool XDELTA = VARLEN && DROP;  // delta from the probabilities (comment above)
-  static_assert(!XDELTA || FUSED_DELTA, "the exact delta is written for the dK / dV kernel that follows");
   __shared__ __attribute__((aligned(16))) unsigned char smem[4 * TILE_BYTES];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
   int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;   // causal: longest-first (fwd)
-  if (!CAUSAL) attn_head_block(P, bh, qb);
+  if (!CAUSAL) attn_head_block(bh, qb);
   const int b = bh / P.H, hh = bh % P.H;
   const int q_blk = qb * 128;
   const int qw = q_blk + wave * 32;
@@ -762,7 +581,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   const bool q_live = VARLEN ? q < Sql : q_ok;
   if constexpr (VARLEN) {
     if (q_blk >= Sql) {  // a wholly dead block: dQ = 0 and zero dbias partials, no tile loop
-      if (q_ok) store_zero_rows<D>(P.dq + b * P.dq_sb + static_cast<int64_t>(q) * P.dq_ss + hh * P.dq_sh, h);
+      if (q_ok) store_zero_rows<D>(P.dq.row(b, q, hh), h);
       if (P.dbq && P.db_ld && qw < P.Sq) {
         float* drow = P.dbq + (static_cast<int64_t>(b) * ((P.Sq + 31) / 32) + qw / 32) * P.db_ld + hh * D;
         for (int c = lane; c < D; c += 64) drow[c] = 0.f;
@@ -774,35 +593,24 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   bf16x8 qf[KS], df[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.p + b * P.q.sb + static_cast<int64_t>(q) * P.q.ss +
-                                                     hh * P.q.sh + ks * 16 + 8 * h)
-                  : bf16x8{};
-    df[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.dout.p + b * P.dout.sb +
-                                                     static_cast<int64_t>(q) * P.dout.ss + hh * P.dout.sh +
-                                                     ks * 16 + 8 * h)
-                  : bf16x8{};
+    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.row(b, q, hh) + ks * 16 + 8 * h) : bf16x8{};
+    df[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.dout.row(b, q, hh) + ks * 16 + 8 * h) : bf16x8{};
   }
   const float lse = q_live ? P.lse[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
-  float dlt;
-  if constexpr (FUSED_DELTA) {
-    // lane (q, h) holds d = 16 ks + 8 h .. +8 of dO row q: a partial dot over
-    // those, then the other half from lane ^ 32
-    float part = 0.f;
-    if (q_live) {
+  // lane (q, h) holds d = 16 ks + 8 h .. +8 of dO row q: a partial dot over
+  // those, then the other half from lane ^ 32
+  float part = 0.f;
+  if (q_live) {
 #pragma unroll
-      for (int ks = 0; ks < KS; ++ks) {
-        const bf16x8 of = *reinterpret_cast<const bf16x8*>(P.o.p + b * P.o.sb + static_cast<int64_t>(q) * P.o.ss +
-                                                           hh * P.o.sh + ks * 16 + 8 * h);
+    for (int ks = 0; ks < KS; ++ks) {
+      const bf16x8 of = *reinterpret_cast<const bf16x8*>(P.o.row(b, q, hh) + ks * 16 + 8 * h);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) part += bf2f(of[e]) * bf2f(df[ks][e]);
-      }
+      for (int e = 0; e < 8; ++e) part += bf2f(of[e]) * bf2f(df[ks][e]);
     }
-    dlt = part + __shfl_xor(part, 32, 64);
-    if constexpr (!XDELTA)  // XDELTA writes the exact delta after the loop
-      if (q_live && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = dlt;
-  } else {
-    dlt = q_live ? P.delta[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
   }
+  const float dlt = part + __shfl_xor(part, 32, 64);
+  if constexpr (!XDELTA)  // XDELTA writes the exact delta after the loop
+    if (q_live && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = dlt;
 
   f32x16 dq[DT];
 #pragma unroll
@@ -822,7 +630,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   // dP of register r with the dropout keep scale applied (DROP only)
   auto kept = [&](float dpv, int k0, int kt, int r) -> float {
     if constexpr (DROP) {
-      const unsigned idx = drow + static_cast<unsigned>(k0) + (kt * 32 + (r & 3) + 8 * (r >> 2));
+      const unsigned idx = drow + static_cast<unsigned>(k0) + (kt * 32 + acc_row(r));
       return dpv * (dropped(idx, dkey, P.drop_thr) ? 0.f : P.drop_rs);
     } else {
       return dpv;
@@ -892,7 +700,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
         if (need_mask) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int key = k0 + kt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int key = k0 + kt * 32 + acc_row(r) + 4 * h;
             float pv = fexp2(s[r] * P.scale_log2 - lse);
             if (key >= Skl || (CAUSAL && key > q) || !q_live) pv = 0.f;
             if constexpr (XDELTA) {
@@ -960,46 +768,33 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   } else if (P.dbq) {
     bias_colsum<DT>(dq, P.scale, P.dbq + hh * D, lane);
   }
-  bf16* row = P.dq + b * P.dq_sb + static_cast<int64_t>(q) * P.dq_ss + hh * P.dq_sh;
-  if (P.wide_store) {
-    store_rows16<DT>(row, dq, P.scale, h, q_ok);
-  } else if (q_ok) {
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        bf16x4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = f2bf(dq[dt][4 * g4 + e] * P.scale);
-        *reinterpret_cast<bf16x4*>(row + dt * 32 + 8 * g4 + 4 * h) = v;
-      }
-  }
+  store_rows16<DT>(P.dq.row(b, q, hh), dq, P.scale, h, q_ok);
 }
 
 // ===========================================================================
-// dK / dV: key block resident (4 waves x NKT*32 keys), loop over 64-query tiles.
+// dK / dV: key block resident (4 waves x 32 keys), loop over 64-query tiles.
 //   S = Q K^T (key on lane) ; P = exp2(S*c - lse[q]) ; dP = dO V^T ;
 //   dS = P (dP - delta[q]) ; dV^T += dO^T P ; dK^T += Q^T dS ; dK = scale*dK
-// NKT = 2 (64 keys per wave): every Q / dO fragment read from LDS feeds two
-// key subtiles, halving LDS traffic per MFMA; slower in practice (register
-// pressure -> 1 wave/SIMD), kept behind FFK_ATTN_BWD_NKT=2 for experiments.
-// DROP (NKT = 1): the key is on the lane and the queries are in the
-// registers, so the hash index q * Sk + key steps by Sk per register; the dP
-// accumulator starts from zero and -delta is added after the keep scale
-// (dS = P (keep rs dP - delta)); dV takes keep . P and rs at the store.
-template <int D, bool CAUSAL, int NKT, bool PF = false, bool DROP = false, bool VARLEN = false>
-__global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
-  static_assert(!PF || NKT == 1, "PF prefetch is written for one key subtile per wave");
-  static_assert(!DROP || NKT == 1, "dropout is written for one key subtile per wave");
-  static_assert(!VARLEN || NKT == 1, "key lengths are written for one key subtile per wave");
-  constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32 * NKT;
+// DROP: the key is on the lane and the queries are in the registers, so the
+// hash index q * Sk + key steps by Sk per register; the dP accumulator starts
+// from zero and -delta is added after the keep scale (dS = P (keep rs dP -
+// delta)); dV takes keep . P and rs at the store.
+template <int D, bool CAUSAL, bool DROP, bool VARLEN>
+__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
+  constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32;
+  // prefetched LDS fragments (below): GPT causal shape 0.341 -> 0.333 ms, BERT
+  // within noise (profiles/ab_attn_bwd_pf_r3.txt).  At D = 128 (one wave /
+  // SIMD) the prefetch registers spill; so they do with dropout at D = 64 (256
+  // registers with no room for the hash: 40 - 72 bytes of scratch, reloaded in
+  // the loop): those forms take the per-pair reads
+  constexpr bool PF = D == 64 && !DROP;
   constexpr int TILE_BYTES = QT * D * 2;
   constexpr int STAGE = 2 * TILE_BYTES + 2 * QT * 4;  // Q, dO, lse, delta
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
   // causal: heads fastest, key block 0 (the most query tiles) first — longest first
   int bh = blockIdx.x, kb = blockIdx.y;
-  if (!CAUSAL) attn_head_block(P, bh, kb);
+  if (!CAUSAL) attn_head_block(bh, kb);
   const int b = bh / P.H, hh = bh % P.H;
   const int k_blk = kb * (4 * KW);
   const int kw = k_blk + wave * KW;
@@ -1023,32 +818,18 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
   };
 
   // K, V rows as B operands (lane holds row `key`, d = 16ks + 8h ..)
-  bf16x8 kf[NKT][KS], vf[NKT][KS];
-  int key[NKT];
-  bool k_ok[NKT];  // the key exists (VARLEN: below the sample's length)
-  bool k_st[NKT];  // the key has a dK / dV row to write (below the physical Sk)
+  bf16x8 kf[KS], vf[KS];
+  const int key = kw + (lane & 31);
+  const bool k_ok = key < Skl();                    // the key exists (VARLEN: below the sample's length)
+  const bool k_st = VARLEN ? key < P.Sk : k_ok;     // the key has a dK / dV row to write (below the physical Sk)
 #pragma unroll
-  for (int j = 0; j < NKT; ++j) {
-    key[j] = kw + 32 * j + (lane & 31);
-    k_ok[j] = key[j] < Skl();
-    k_st[j] = VARLEN ? key[j] < P.Sk : k_ok[j];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      kf[j][ks] = k_ok[j] ? *reinterpret_cast<const bf16x8*>(P.k.p + b * P.k.sb +
-                                                             static_cast<int64_t>(key[j]) * P.k.ss + hh * P.k.sh +
-                                                             ks * 16 + 8 * h)
-                          : bf16x8{};
-      vf[j][ks] = k_ok[j] ? *reinterpret_cast<const bf16x8*>(P.v.p + b * P.v.sb +
-                                                             static_cast<int64_t>(key[j]) * P.v.ss + hh * P.v.sh +
-                                                             ks * 16 + 8 * h)
-                          : bf16x8{};
-    }
+  for (int ks = 0; ks < KS; ++ks) {
+    kf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.k.row(b, key, hh) + ks * 16 + 8 * h) : bf16x8{};
+    vf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.v.row(b, key, hh) + ks * 16 + 8 * h) : bf16x8{};
   }
-  f32x16 dk[NKT][DT], dv[NKT][DT];
+  f32x16 dk[DT], dv[DT];
 #pragma unroll
-  for (int j = 0; j < NKT; ++j)
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt) dk[j][dt] = dv[j][dt] = f32x16{};
+  for (int dt = 0; dt < DT; ++dt) dk[dt] = dv[dt] = f32x16{};
 
   // VARLEN: a key block wholly past the length skips the query loop and
   // stores zeros (dK = dV = 0, and zero partials into the dbias slab); the
@@ -1056,11 +837,11 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
   const int n_q_tiles = (VARLEN && k_blk >= Skl()) ? 0 : (Sql() + QT - 1) / QT;
   const int t0 = CAUSAL ? (k_blk / QT) : 0;
   // dropout: hash index of register r of a subtile = (first query + 4 h +
-  // (r & 3) + 8 (r >> 2)) * Sk + key
+  // acc_row(r)) * Sk + key
   [[maybe_unused]] unsigned dkey = 0, dcol = 0;
   if constexpr (DROP) {
     dkey = drop_key(P, bh);
-    dcol = 4u * h * static_cast<unsigned>(P.Sk) + static_cast<unsigned>(key[0]);
+    dcol = 4u * h * static_cast<unsigned>(P.Sk) + static_cast<unsigned>(key);
   }
 
   TileLoader<D, QT> ql, dl;
@@ -1135,12 +916,12 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
       const int hl = ln >> 5;
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
-        f32x16 s[NKT], dp[NKT];
+        f32x16 s, dp;
         // PF: every LDS fragment of this 32-query subtile is requested before
         // the MFMAs that consume it — the row fragments of S / dP ahead of
         // the first product, the transposed fragments of dV / dK under the
         // S / dP products and the exp2 pass — instead of one read pair per
-        // MFMA pair, each waiting out the LDS latency (FFK_ATTN_BWD_PF)
+        // MFMA pair, each waiting out the LDS latency
         [[maybe_unused]] bf16x8 qa_pf[PF ? KS : 1], da_pf[PF ? KS : 1];
         [[maybe_unused]] bf16x8 tda_pf[PF ? 2 : 1][PF ? DT : 1], tqa_pf[PF ? 2 : 1][PF ? DT : 1];
         if constexpr (PF) {
@@ -1152,19 +933,17 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
           }
         }
 #pragma unroll
-        for (int j = 0; j < NKT; ++j)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int ql_ = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            s[j][r] = ls[ql_];
-            dp[j][r] = DROP ? 0.f : ds[ql_];
-          }
+        for (int r = 0; r < 16; ++r) {
+          const int ql_ = qt * 32 + acc_row(r) + 4 * h;
+          s[r] = ls[ql_];
+          dp[r] = DROP ? 0.f : ds[ql_];
+        }
         prio_hi(P);
         if constexpr (PF) {
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            s[0] = mfma32(qa_pf[ks], kf[0][ks], s[0]);
-            dp[0] = mfma32(da_pf[ks], vf[0][ks], dp[0]);
+            s = mfma32(qa_pf[ks], kf[ks], s);
+            dp = mfma32(da_pf[ks], vf[ks], dp);
           }
 #pragma unroll
           for (int st = 0; st < 2; ++st)
@@ -1178,56 +957,44 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
           for (int ks = 0; ks < KS; ++ks) {
             const int off = lds_off<D>(qt * 32 + (ln & 31), 2 * ks + hl);
             const bf16x8 qa = lds_read16(Qt, off), da = lds_read16(Dt, off);
-#pragma unroll
-            for (int j = 0; j < NKT; ++j) {
-              s[j] = mfma32(qa, kf[j][ks], s[j]);
-              dp[j] = mfma32(da, vf[j][ks], dp[j]);
-            }
+            s = mfma32(qa, kf[ks], s);
+            dp = mfma32(da, vf[ks], dp);
           }
         }
         prio_lo(P);
+        if constexpr (DROP) {
+          const unsigned dq0 = static_cast<unsigned>(q0 + qt * 32) * static_cast<unsigned>(P.Sk) + dcol;
 #pragma unroll
-        for (int j = 0; j < NKT; ++j) {
-          if constexpr (DROP) {
-            const unsigned dq0 = static_cast<unsigned>(q0 + qt * 32) * static_cast<unsigned>(P.Sk) + dcol;
+          for (int r = 0; r < 16; ++r) {
+            const int rq = acc_row(r);
+            const int qq = q0 + qt * 32 + rq + 4 * h;
+            float pv = fexp2(s[r] * P.scale_log2);
+            if (need_mask && (qq >= Sql() || (CAUSAL && key > qq) || !k_ok)) pv = 0.f;
+            const bool drop = dropped(dq0 + static_cast<unsigned>(rq) * static_cast<unsigned>(P.Sk), dkey, P.drop_thr);
+            dp[r] = pv * fmaf(drop ? 0.f : P.drop_rs, dp[r], ds[qt * 32 + rq + 4 * h]);
+            s[r] = drop ? 0.f : pv;
+          }
+        } else if (need_mask) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int rq = (r & 3) + 8 * (r >> 2);
-              const int qq = q0 + qt * 32 + rq + 4 * h;
-              float pv = fexp2(s[j][r] * P.scale_log2);
-              if (need_mask && (qq >= Sql() || (CAUSAL && key[j] > qq) || !k_ok[j])) pv = 0.f;
-              const bool drop =
-                  dropped(dq0 + static_cast<unsigned>(rq) * static_cast<unsigned>(P.Sk), dkey, P.drop_thr);
-              dp[j][r] = pv * fmaf(drop ? 0.f : P.drop_rs, dp[j][r], ds[qt * 32 + rq + 4 * h]);
-              s[j][r] = drop ? 0.f : pv;
-            }
-          } else if (need_mask) {
+          for (int r = 0; r < 16; ++r) {
+            const int qq = q0 + qt * 32 + acc_row(r) + 4 * h;
+            float pv = fexp2(s[r] * P.scale_log2);
+            if (qq >= Sql() || (CAUSAL && key > qq) || !k_ok) pv = 0.f;
+            s[r] = pv;
+            dp[r] = pv * dp[r];
+          }
+        } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int qq = q0 + qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-              float pv = fexp2(s[j][r] * P.scale_log2);
-              if (qq >= Sql() || (CAUSAL && key[j] > qq) || !k_ok[j]) pv = 0.f;
-              s[j][r] = pv;
-              dp[j][r] = pv * dp[j][r];
-            }
-          } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float pv = fexp2(s[j][r] * P.scale_log2);
-              s[j][r] = pv;
-              dp[j][r] = pv * dp[j][r];
-            }
+          for (int r = 0; r < 16; ++r) {
+            const float pv = fexp2(s[r] * P.scale_log2);
+            s[r] = pv;
+            dp[r] = pv * dp[r];
           }
         }
         prio_hi(P);
 #pragma unroll
         for (int st = 0; st < 2; ++st) {
-          bf16x8 pf[NKT], sf[NKT];
-#pragma unroll
-          for (int j = 0; j < NKT; ++j) {
-            pf[j] = acc_to_frag(s[j], st);
-            sf[j] = acc_to_frag(dp[j], st);
-          }
+          const bf16x8 pf = acc_to_frag(s, st), sf = acc_to_frag(dp, st);
 #pragma unroll
           for (int dt = 0; dt < DT; ++dt) {
             bf16x8 da, qa;
@@ -1238,11 +1005,8 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
               da = tr_frag<D>(Dt, qt * 32 + 16 * st, dt, ln);
               qa = tr_frag<D>(Qt, qt * 32 + 16 * st, dt, ln);
             }
-#pragma unroll
-            for (int j = 0; j < NKT; ++j) {
-              dv[j][dt] = mfma32(da, pf[j], dv[j][dt]);
-              dk[j][dt] = mfma32(qa, sf[j], dk[j][dt]);
-            }
+            dv[dt] = mfma32(da, pf, dv[dt]);
+            dk[dt] = mfma32(qa, sf, dk[dt]);
           }
         }
         prio_lo(P);
@@ -1258,42 +1022,19 @@ __global__ __launch_bounds__(256, (D == 64 && NKT == 1 ? 2 : 1)) void attn_bwd_d
   }
   float vmul = 1.f;  // dV's store scale: the dropout keep scale
   if constexpr (DROP) vmul = P.drop_rs;
-#pragma unroll
-  for (int j = 0; j < NKT; ++j) {
-    if (P.db_ld) {
-      if (kw + 32 * j >= P.Sk) continue;
-      const int64_t roff = (static_cast<int64_t>(b) * ((P.Sk + 31) / 32) + (kw + 32 * j) / 32) * P.db_ld + hh * D;
-      if (P.dbk) bias_partial<DT>(dk[j], P.scale, P.dbk + roff, lane);
-      if (P.dbv) bias_partial<DT>(dv[j], vmul, P.dbv + roff, lane);
-    } else {
-      if (P.dbk) bias_colsum<DT>(dk[j], P.scale, P.dbk + hh * D, lane);
-      if (P.dbv) bias_colsum<DT>(dv[j], vmul, P.dbv + hh * D, lane);
+  if (P.db_ld) {
+    if (kw < P.Sk) {  // waves wholly past the sequence own no slab row
+      const int64_t roff = (static_cast<int64_t>(b) * ((P.Sk + 31) / 32) + kw / 32) * P.db_ld + hh * D;
+      if (P.dbk) bias_partial<DT>(dk, P.scale, P.dbk + roff, lane);
+      if (P.dbv) bias_partial<DT>(dv, vmul, P.dbv + roff, lane);
     }
+  } else {
+    if (P.dbk) bias_colsum<DT>(dk, P.scale, P.dbk + hh * D, lane);
+    if (P.dbv) bias_colsum<DT>(dv, vmul, P.dbv + hh * D, lane);
   }
-#pragma unroll
-  for (int j = 0; j < NKT; ++j) {
-    bf16* krow = P.dk + b * P.dk_sb + static_cast<int64_t>(key[j]) * P.dk_ss + hh * P.dk_sh;
-    bf16* vrow = P.dv + b * P.dv_sb + static_cast<int64_t>(key[j]) * P.dv_ss + hh * P.dv_sh;
-    if (P.wide_store) {   // every lane swaps; k_st guards the stores
-      store_rows16<DT>(krow, dk[j], P.scale, h, k_st[j]);
-      store_rows16<DT>(vrow, dv[j], vmul, h, k_st[j]);
-      continue;
-    }
-    if (!k_st[j]) continue;
-#pragma unroll
-    for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) {
-        bf16x4 a, c;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          a[e] = f2bf(dk[j][dt][4 * g4 + e] * P.scale);
-          c[e] = f2bf(DROP ? dv[j][dt][4 * g4 + e] * vmul : dv[j][dt][4 * g4 + e]);
-        }
-        *reinterpret_cast<bf16x4*>(krow + dt * 32 + 8 * g4 + 4 * h) = a;
-        *reinterpret_cast<bf16x4*>(vrow + dt * 32 + 8 * g4 + 4 * h) = c;
-      }
-  }
+  // every lane swaps; k_st guards the stores
+  store_rows16<DT>(P.dk.row(b, key, hh), dk, P.scale, h, k_st);
+  store_rows16<DT>(P.dv.row(b, key, hh), dv, vmul, h, k_st);
 }
 
 // ===========================================================================
@@ -1380,9 +1121,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, 
     bf16x8 vf[KS];
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      vf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.v.p + b * P.v.sb + static_cast<int64_t>(key) * P.v.ss +
-                                                       hh * P.v.sh + ks * 16 + 8 * h)
-                    : bf16x8{};
+      vf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.v.row(b, key, hh) + ks * 16 + 8 * h) : bf16x8{};
     }
     {
       // K image of the block: 4 rows per thread, 64 apart.  The row index is
@@ -1391,7 +1130,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, 
       // across the tile loop.
       int r0 = srow;
       asm volatile("" : "+v"(r0));
-      const bf16* kp = P.k.p + b * P.k.sb + static_cast<int64_t>(k_blk + r0) * P.k.ss + hh * P.k.sh + sch * 8;
+      const bf16* kp = P.k.row(b, k_blk + r0, hh) + sch * 8;
       bf16x8 kr[KB / 64];
 #pragma unroll
       for (int i = 0; i < KB / 64; ++i)
@@ -1452,8 +1191,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, 
       }
       if (last_kb) {
         const int q = t * QT + dq_q + (lane & 31);
-        bf16* row = P.dq + b * P.dq_sb + static_cast<int64_t>(q) * P.dq_ss + hh * P.dq_sh + dq_d;
-        store_rows16<1>(row, acc, P.scale, h, q < P.Sq);
+        store_rows16<1>(P.dq.row(b, q, hh) + dq_d, acc, P.scale, h, q < P.Sq);
       } else {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -1498,7 +1236,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, 
           }
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const int ql_ = qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int ql_ = qt * 32 + acc_row(r) + 4 * h;
             s[r] = ls[ql_];
             dp[r] = ds[ql_];
           }
@@ -1517,7 +1255,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, 
           if (need_mask) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-              const int qq = q0 + qt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+              const int qq = q0 + qt * 32 + acc_row(r) + 4 * h;
               float pv = fexp2(s[r] * P.scale_log2);
               if (qq >= P.Sq || !k_ok) pv = 0.f;
               s[r] = pv;
@@ -1566,10 +1304,8 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, 
       __syncthreads();
     }
 
-    bf16* krow = P.dk + b * P.dk_sb + static_cast<int64_t>(key) * P.dk_ss + hh * P.dk_sh;
-    bf16* vrow = P.dv + b * P.dv_sb + static_cast<int64_t>(key) * P.dv_ss + hh * P.dv_sh;
-    store_rows16<DT>(krow, dk, P.scale, h, k_ok);
-    store_rows16<DT>(vrow, dv, 1.f, h, k_ok);
+    store_rows16<DT>(P.dk.row(b, key, hh), dk, P.scale, h, k_ok);
+    store_rows16<DT>(P.dv.row(b, key, hh), dv, 1.f, h, k_ok);
   }
 }
 
@@ -1579,19 +1315,18 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
   auto tv = [](const AttnTensors::T& x) {
     return TensorView{static_cast<const bf16*>(x.p), x.sb, x.ss, x.sh};
   };
+  auto ov = [](const AttnTensors::T& x) {
+    return OutView{static_cast<bf16*>(const_cast<void*>(x.p)), x.sb, x.ss, x.sh};
+  };
   P.q = tv(t.q);
   P.k = tv(t.k);
   P.v = tv(t.v);
   P.o = tv(t.o);
   P.dout = tv(t.dout);
-  P.o_out = static_cast<bf16*>(const_cast<void*>(t.o.p));
-  P.o_sb = t.o.sb; P.o_ss = t.o.ss; P.o_sh = t.o.sh;
-  P.dq = static_cast<bf16*>(const_cast<void*>(t.dq.p));
-  P.dq_sb = t.dq.sb; P.dq_ss = t.dq.ss; P.dq_sh = t.dq.sh;
-  P.dk = static_cast<bf16*>(const_cast<void*>(t.dk.p));
-  P.dk_sb = t.dk.sb; P.dk_ss = t.dk.ss; P.dk_sh = t.dk.sh;
-  P.dv = static_cast<bf16*>(const_cast<void*>(t.dv.p));
-  P.dv_sb = t.dv.sb; P.dv_ss = t.dv.ss; P.dv_sh = t.dv.sh;
+  P.o_out = ov(t.o);
+  P.dq = ov(t.dq);
+  P.dk = ov(t.dk);
+  P.dv = ov(t.dv);
   P.lse = t.lse;
   P.delta = t.delta;
   P.dbq = t.dbq;
@@ -1609,11 +1344,6 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
     return e ? atoi(e) : -1;
   }();
   P.prio = prio >= 0 ? prio : (D == 128 ? 1 : 0);
-  // read per call: tools/attn_time.py --xcd-ab switches it inside one process
-  const char* xe = getenv("FFK_ATTN_XCD");
-  P.xcd = xe ? atoi(xe) : 1;
-  const char* we = getenv("FFK_ATTN_WIDE_STORE");
-  P.wide_store = we ? atoi(we) : 1;
   if (t.drop_threshold) {
     if (t.drop_threshold >= (1u << 24)) throw std::invalid_argument("attention: dropout threshold must be below 2^24");
     if (static_cast<uint64_t>(Sq) * static_cast<uint64_t>(Sk) >= (1ull << 32))
@@ -1628,166 +1358,81 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
   return P;
 }
 
+// The runtime (D, causal) as compile-time constants: f(integral_constant<int,
+// D>, bool_constant<causal>).
+template <class F>
+static void with_head(int D, bool causal, F&& f) {
+  auto on_causal = [&](auto d) {
+    if (causal) f(d, std::true_type{});
+    else f(d, std::false_type{});
+  };
+  if (D == 64) on_causal(std::integral_constant<int, 64>{});
+  else if (D == 128) on_causal(std::integral_constant<int, 128>{});
+  else throw std::invalid_argument("attention: head dim must be 64 or 128");
+}
+// The same for (dropout, lengths): f(bool_constant<drop>, bool_constant<varlen>).
+template <class F>
+static void with_features(bool drop, bool varlen, F&& f) {
+  auto on_varlen = [&](auto dr) {
+    if (varlen) f(dr, std::true_type{});
+    else f(dr, std::false_type{});
+  };
+  if (drop) on_varlen(std::true_type{});
+  else on_varlen(std::false_type{});
+}
+
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st) {
   AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
   const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nbh = static_cast<unsigned>(B * H);
   dim3 grid = causal ? dim3(nbh, nq) : dim3(nq, nbh), block(256);
-  // read per call (not cached): the A/B tests switch it inside one process.
-  // Opt-in: 2 waves / SIMD (226 VGPRs) against the default's 3, and slower at
-  // both bench shapes (BERT 0.145 vs 0.118 ms, GPT causal 0.253 vs 0.212 ms,
-  // profiles/r4/attn_pipe_ab_r4.jsonl): the third wave hides more than the
-  // in-wave overlap gains
-  const char* pe = getenv("FFK_ATTN_FWD_PIPE");
-  const int pipe = pe ? atoi(pe) : 0;
-  if (P.kv_lens || P.q_lens) {  // key / query lengths: the default variant only, like dropout
-#define FFK_ATTN_FWD_VL(DD, CC)                                                                  \
-  if (P.drop_thr) hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, true, true>), grid, block, 0, st, P); \
-  else hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, false, true>), grid, block, 0, st, P)
-    if (D == 64) {
-      if (causal) { FFK_ATTN_FWD_VL(64, true); }
-      else { FFK_ATTN_FWD_VL(64, false); }
-    } else if (D == 128) {
-      if (causal) { FFK_ATTN_FWD_VL(128, true); }
-      else { FFK_ATTN_FWD_VL(128, false); }
-    } else {
-      throw std::invalid_argument("attention: head dim must be 64 or 128");
-    }
-#undef FFK_ATTN_FWD_VL
-    FFK_LAUNCH_CHECK("attention_fwd");
-    return;
-  }
-  if (P.drop_thr) {  // dropout: the default variant only, whatever the experimental switches say
-    if (D == 64) {
-      if (causal) hipLaunchKernelGGL((attn_fwd_kernel<64, true, true>), grid, block, 0, st, P);
-      else hipLaunchKernelGGL((attn_fwd_kernel<64, false, true>), grid, block, 0, st, P);
-    } else if (D == 128) {
-      if (causal) hipLaunchKernelGGL((attn_fwd_kernel<128, true, true>), grid, block, 0, st, P);
-      else hipLaunchKernelGGL((attn_fwd_kernel<128, false, true>), grid, block, 0, st, P);
-    } else {
-      throw std::invalid_argument("attention: head dim must be 64 or 128");
-    }
-    FFK_LAUNCH_CHECK("attention_fwd");
-    return;
-  }
-  if (pipe && D == 64) {
-    if (causal) hipLaunchKernelGGL((attn_fwd_pipe_kernel<64, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_fwd_pipe_kernel<64, false>), grid, block, 0, st, P);
-    FFK_LAUNCH_CHECK("attention_fwd");
-    return;
-  }
-  if (D == 64) {
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_fwd_kernel<64, false>), grid, block, 0, st, P);
-  } else if (D == 128) {
-    if (causal) hipLaunchKernelGGL((attn_fwd_kernel<128, true>), grid, block, 0, st, P);
-    else hipLaunchKernelGGL((attn_fwd_kernel<128, false>), grid, block, 0, st, P);
-  } else {
-    throw std::invalid_argument("attention: head dim must be 64 or 128");
-  }
+  with_head(D, causal, [&](auto d, auto c) {
+    with_features(P.drop_thr != 0, P.kv_lens || P.q_lens, [&](auto dr, auto vl) {
+      constexpr int DD = decltype(d)::value;
+      constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
+      hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, VL>), grid, block, 0, st, P);
+    });
+  });
   FFK_LAUNCH_CHECK("attention_fwd");
 }
 
-template <int D, bool CAUSAL, bool DROP = false, bool VARLEN = false>
-static void launch_dkdv(int nkt, dim3 grid, dim3 block, hipStream_t st, const AttnParams& P) {
-  if constexpr (D == 64 && !DROP && !VARLEN) {
-    if (nkt == 2) {
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 2>), grid, block, 0, st, P);
-      return;
-    }
-  }
-  // default on: GPT causal shape 0.341 -> 0.333 ms, BERT within noise
-  // (profiles/ab_attn_bwd_pf_r3.txt); FFK_ATTN_BWD_PF=0 for the per-pair reads
-  static const int pf = [] {
-    const char* e = getenv("FFK_ATTN_BWD_PF");
-    return e ? atoi(e) : 1;
-  }();
-  // at D = 128 (one wave / SIMD) the prefetch registers spill; so they do with
-  // dropout at D = 64 (256 registers with no room for the hash: 40 - 72 bytes
-  // of scratch, reloaded in the loop), which takes the per-pair reads
-  if constexpr (!DROP) {
-    if (pf && D == 64) {
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, D == 64, false, VARLEN>), grid, block, 0, st, P);
-      return;
-    }
-  }
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<D, CAUSAL, 1, false, DROP, VARLEN>), grid, block, 0, st, P);
-}
-
-// The one-pass kernel's shapes; both switches are read per call (the A/B tool
-// and the tests flip them inside one process).  FFK_ATTN_BWD_FUSED_DELTA=0
-// asks for the three-launch path and so also rules the one-pass kernel out.
-static bool onepass_eligible(int Sk, int D, bool causal, bool dbias, bool drop = false, bool varlen = false) {
-  if (D != 64 || causal || Sk > 512 || dbias || drop || varlen) return false;
+// The one-pass kernel's shapes.  `extras` is any of dbias, dropout and
+// lengths: the kernel pair only.  The switch is read per call (the A/B tool
+// and the tests flip it inside one process).
+static bool onepass_eligible(int Sk, int D, bool causal, bool extras) {
+  if (D != 64 || causal || Sk > 512 || extras) return false;
   const char* oe = getenv("FFK_ATTN_BWD_ONEPASS");
-  const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
-  return (oe ? atoi(oe) != 0 : true) && (fde ? atoi(fde) != 0 : true);
+  return oe ? atoi(oe) != 0 : true;
 }
 
 int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias, bool varlen) {
-  if (!onepass_eligible(Sk, D, causal, dbias, false, varlen) || Sk <= 256) return 0;
+  if (!onepass_eligible(Sk, D, causal, dbias || varlen) || Sk <= 256) return 0;
   return static_cast<int64_t>(B) * H * ((Sq + 63) / 64) * 64 * 64;
 }
 
 int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                   hipStream_t st, float* ws) {
   AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
+  const bool drop = P.drop_thr != 0, varlen = P.kv_lens || P.q_lens;
   // a second key block needs the workspace: callers that pass none keep the
   // two-kernel path
-  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv, P.drop_thr != 0, P.kv_lens || P.q_lens) &&
-      (Sk <= 256 || ws)) {
+  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv || drop || varlen) && (Sk <= 256 || ws)) {
     hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(static_cast<unsigned>(B * H)), dim3(512), 0, st, P, ws);
     FFK_LAUNCH_CHECK("attention_bwd");
     return 1;
   }
-  const int64_t rows = static_cast<int64_t>(B) * H * Sq;
-  const int tpr = D / 8;
-  dim3 gd(static_cast<unsigned>((rows * tpr + 255) / 256));
-  static const int nkt_env = [] {
-    const char* e = getenv("FFK_ATTN_BWD_NKT");
-    return e ? atoi(e) : 0;
-  }();
-  // NKT = 2 (64 keys per wave) halves LDS reads per MFMA but needs ~500
-  // registers (1 wave/SIMD, spills when causal): measured 0.24 vs 0.21 ms
-  // (BERT shape) and 0.92 vs 0.56 ms (GPT causal) — opt-in only.
-  // (dropout and key / query lengths: the default variants only, NKT = 1 and
-  // the fused delta)
-  const bool varlen = P.kv_lens || P.q_lens;
-  const int nkt = D == 64 && nkt_env == 2 && !P.drop_thr && !varlen ? 2 : 1;
-  const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nbh = static_cast<unsigned>(B * H);
-  const unsigned nk = static_cast<unsigned>((Sk + 128 * nkt - 1) / (128 * nkt));
+  const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nk = static_cast<unsigned>((Sk + 127) / 128);
+  const unsigned nbh = static_cast<unsigned>(B * H);
   dim3 gq = causal ? dim3(nbh, nq) : dim3(nq, nbh), gk = causal ? dim3(nbh, nk) : dim3(nk, nbh), block(256);
-  // read per call: the A/B tool switches it inside one process
-  const char* fde = getenv("FFK_ATTN_BWD_FUSED_DELTA");
-  const bool fused_delta = fde ? atoi(fde) != 0 : true;
-#define FFK_ATTN_BWD(DD, CC)                                                          \
-  if (varlen && P.drop_thr) {                                                         \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, true, true>), gq, block, 0, st, P);  \
-    launch_dkdv<DD, CC, true, true>(nkt, gk, block, st, P);                           \
-  } else if (varlen) {                                                                \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, false, true>), gq, block, 0, st, P); \
-    launch_dkdv<DD, CC, false, true>(nkt, gk, block, st, P);                          \
-  } else if (P.drop_thr) {                                                            \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true, true>), gq, block, 0, st, P);\
-    launch_dkdv<DD, CC, true>(nkt, gk, block, st, P);                                 \
-  } else if (fused_delta) {                                                           \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, true>), gq, block, 0, st, P);      \
-    launch_dkdv<DD, CC>(nkt, gk, block, st, P);                                       \
-  } else {                                                                            \
-    hipLaunchKernelGGL((attn_bwd_delta_kernel<DD>), gd, block, 0, st, P);             \
-    launch_dkdv<DD, CC>(nkt, gk, block, st, P);                                       \
-    hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC>), gq, block, 0, st, P);            \
-  }
-  if (D == 64) {
-    if (causal) { FFK_ATTN_BWD(64, true); }
-    else { FFK_ATTN_BWD(64, false); }
-  } else if (D == 128) {
-    if (causal) { FFK_ATTN_BWD(128, true); }
-    else { FFK_ATTN_BWD(128, false); }
-  } else {
-    throw std::invalid_argument("attention: head dim must be 64 or 128");
-  }
-#undef FFK_ATTN_BWD
+  // dQ first: it writes the delta that the dK / dV kernel reads
+  with_head(D, causal, [&](auto d, auto c) {
+    with_features(drop, varlen, [&](auto dr, auto vl) {
+      constexpr int DD = decltype(d)::value;
+      constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, VL>), gq, block, 0, st, P);
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, VL>), gk, block, 0, st, P);
+    });
+  });
   FFK_LAUNCH_CHECK("attention_bwd");
   return 0;
 }

@@ -119,11 +119,12 @@ struct AttnTensors {
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st);
 // Returns the path that ran: 1 = the one-pass kernel (D = 64, non-causal,
-// Sk <= 512, no dbias, no dropout, no key or query lengths; FFK_ATTN_BWD_ONEPASS=0 turns
-// it off), 0 = the dQ and
-// dK/dV kernels.  With Sk > 256 the one-pass kernel needs `ws`, an fp32
-// scratch of attention_bwd_workspace() floats (0: the call is not eligible
-// or needs none).
+// Sk <= 512, no dbias, no dropout, no key or query lengths;
+// FFK_ATTN_BWD_ONEPASS=0, read per call, turns it off), 0 = the dQ kernel
+// (which also writes delta = rowsum(dO * O)) followed by the dK/dV kernel.
+// With Sk > 256 the one-pass kernel needs `ws`, an fp32 scratch of
+// attention_bwd_workspace() floats (0: the call is not eligible or needs
+// none).
 int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal, bool dbias,
                                 bool varlen = false);
 int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,

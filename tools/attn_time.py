@@ -4,10 +4,12 @@ and GPT-3-medium shapes; FF_PKG_ROOT selects the package tree (same-box A/B of
 two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
 
     python tools/attn_time.py [iters]
-    python tools/attn_time.py --pipe-ab | --delta-ab | --onepass-ab   (same-process A/B of a kernel switch)
+    python tools/attn_time.py --onepass-ab                            (same-process A/B of the one-pass backward)
     python tools/attn_time.py --dropout 0.1                           (attention dropout against p = 0)
     python tools/attn_time.py --varlen [--dropout 0.1]                (per-sample key lengths against full length)
     python tools/attn_time.py --varlen --queries [--dropout 0.1]      (the same lengths as query lengths too)
+
+--d128 appends two D = 128 shapes to whichever mode is run.
 """
 import json
 import os
@@ -22,6 +24,9 @@ from flexflow_train_amd import kernels as K  # noqa: E402
 SHAPES = {"bert-large": (64, 512, 16, 64, False), "gpt3-medium": (16, 2048, 16, 64, True),
           # the shipped bench batches
           "bert-large-b128": (128, 512, 16, 64, False), "gpt3-medium-b32": (32, 2048, 16, 64, True)}
+if "--d128" in sys.argv:
+    sys.argv.remove("--d128")
+    SHAPES.update({"d128": (8, 1024, 16, 128, False), "d128-causal": (8, 1024, 16, 128, True)})
 
 
 def _time(fn, iters):
@@ -69,7 +74,7 @@ def env_ab(var, which, iters, rounds=5):
 
 def pmc_run(n=5):
     """A few dispatches of each kernel for a counter pass (rocprofv3 --pmc):
-    forward default, forward pipelined, backward, at both bench shapes."""
+    forward and backward, at both bench shapes."""
     for name, (B, S, H, D, causal) in SHAPES.items():
         g = torch.Generator(device="cuda").manual_seed(0)
         qkv = torch.randn(B, S, 3, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
@@ -77,11 +82,8 @@ def pmc_run(n=5):
         do = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
         dqkv = torch.empty_like(qkv)
         o, lse = K.attention_fwd(q, k, v, causal=causal)
-        for p in ("0", "1"):
-            os.environ["FFK_ATTN_FWD_PIPE"] = p
-            for _ in range(n):
-                K.attention_fwd(q, k, v, causal=causal, out=o)
-        os.environ.pop("FFK_ATTN_FWD_PIPE", None)
+        for _ in range(n):
+            K.attention_fwd(q, k, v, causal=causal, out=o)
         for p in ("0", "1"):   # the dQ + dK/dV kernels, then the one-pass kernel where it applies
             os.environ["FFK_ATTN_BWD_ONEPASS"] = p
             for _ in range(n):
@@ -190,18 +192,8 @@ def main():
         return dropout_ab(float(sys.argv[sys.argv.index("--dropout") + 1]), 30)
     if "--pmc-run" in sys.argv:
         return pmc_run()
-    if "--pipe-ab" in sys.argv:        # software-pipelined forward
-        return env_ab("FFK_ATTN_FWD_PIPE", "fwd", 50)
-    if "--delta-ab" in sys.argv:       # delta fused into the dQ kernel
-        return env_ab("FFK_ATTN_BWD_FUSED_DELTA", "bwd", 30)
     if "--onepass-ab" in sys.argv:     # one-pass backward (BERT shapes; the causal shapes are not eligible)
         return env_ab("FFK_ATTN_BWD_ONEPASS", "bwd", 30)
-    if "--wide-ab" in sys.argv:        # 16-B output row stores (forward / backward epilogues)
-        env_ab("FFK_ATTN_WIDE_STORE", "fwd", 50)
-        return env_ab("FFK_ATTN_WIDE_STORE", "bwd", 30)
-    if "--xcd-ab" in sys.argv:         # XCD-local head order (non-causal grids)
-        env_ab("FFK_ATTN_XCD", "fwd", 50)
-        return env_ab("FFK_ATTN_XCD", "bwd", 30)
     iters = int(sys.argv[1]) if len(sys.argv) > 1 else 50
     for name, (B, S, H, D, causal) in SHAPES.items():
         g = torch.Generator(device="cuda").manual_seed(0)
