@@ -584,14 +584,27 @@ OpSpec embedding_spec() {
 // query length (self-attention over a padded batch): queries at or past it do
 // not exist either.  One tensor bounds both axes, so it needs key_lengths and
 // equal query and key sequence extents.  Absent by default, like key_lengths.
+// With the attribute packed_sequences = M (M >= 1) the batch is packed: every
+// row ("pack") of q holds up to M sequences end to end, and the fourth input
+// is their lengths, rank 2 [batch, M] (0: an empty slot).  Attention is
+// self-attention inside each sequence; tokens past a pack's last sequence see
+// nothing.  max_seqlen (default: the sequence extent T; 1 .. T) bounds a
+// sequence's length.  Exclusive with key_lengths / query_lengths, needs equal
+// q / k / v sequence extents and an unpartitioned sequence dim.  Data
+// parallelism shards packs: a pack is self-contained.  Both attributes are
+// absent by default.
 bool mha_has_lengths(const OpAttrs& a) { return a.has("key_lengths") && a.b("key_lengths"); }
+bool mha_is_packed(const OpAttrs& a) { return a.has("packed_sequences") && a.i("packed_sequences") > 0; }
+int64_t mha_max_seqlen(const OpAttrs& a, int64_t T) {
+  return a.has("max_seqlen") && a.i("max_seqlen") > 0 ? a.i("max_seqlen") : T;
+}
 bool mha_has_query_lengths(const OpAttrs& a) { return a.has("query_lengths") && a.b("query_lengths"); }
 bool is_integer_dtype(DataType t) { return t == DataType::INT32 || t == DataType::INT64; }
 
 OpSpec mha_spec() {
   OpSpec s;
   s.num_inputs = 3;
-  s.arity = [](const OpAttrs& a) { return mha_has_lengths(a) ? 4 : 3; };
+  s.arity = [](const OpAttrs& a) { return (mha_has_lengths(a) || mha_is_packed(a)) ? 4 : 3; };
   s.required = {"embed_dim", "num_heads"};
   s.defaults = {{"kdim", int64_t(0)}, {"vdim", int64_t(0)}, {"dropout", 0.0}, {"bias", true},
                 {"add_bias_kv", false}, {"add_zero_attn", false}, {"causal", false},
@@ -612,7 +625,24 @@ OpSpec mha_spec() {
   };
   s.out = [](const OpAttrs& a, const Shapes& in) {
     for (int i = 0; i < 3; ++i) require(nd(in[i]) == 3, a, "q/k/v must be [batch, seq, feature]");
-    if (in.size() > 3) {
+    if (a.has("packed_sequences")) require(a.i("packed_sequences") >= 1, a, "packed_sequences must be at least 1");
+    if (a.has("max_seqlen")) require(mha_is_packed(a), a, "max_seqlen needs packed_sequences");
+    if (mha_is_packed(a)) {
+      require(!mha_has_lengths(a) && !mha_has_query_lengths(a), a,
+              "packed_sequences excludes key_lengths / query_lengths");
+      if (in.size() > 3) {  // (parallel inference re-enters with q, k, v alone)
+        require(nd(in[3]) == 2, a, "packed_sequences: segment lengths must be rank 2 [batch, M]");
+        require(is_integer_dtype(in[3].dtype), a, "packed_sequences: segment lengths must have an integer dtype");
+        require(in[3].dims[0] == in[0].dims[0], a, "packed_sequences: segment lengths batch mismatch");
+        require(in[3].dims[1] == a.i("packed_sequences"), a,
+                "packed_sequences: segment lengths dim 1 differs from M");
+      }
+      require(in[0].dims[1] == in[1].dims[1] && in[1].dims[1] == in[2].dims[1], a,
+              "packed_sequences needs equal q / k / v sequence extents (self-attention inside each sequence)");
+      const int64_t ms = mha_max_seqlen(a, in[0].dims[1]);
+      require(!a.has("max_seqlen") || (a.i("max_seqlen") >= 1 && ms <= in[0].dims[1]), a,
+              "max_seqlen must lie in 1 .. the sequence extent");
+    } else if (in.size() > 3) {
       require(nd(in[3]) == 1, a, "key lengths must be rank 1 [batch]");
       require(is_integer_dtype(in[3].dtype), a, "key lengths must have an integer dtype");
       require(in[3].dims[0] == in[0].dims[0], a, "key lengths batch mismatch");
@@ -643,7 +673,21 @@ OpSpec mha_spec() {
       require(t.sum_degree == 1, a, "attention inputs cannot be partial sums");
       require(t.dim(2).degree == 1, a, "feature dim must be unpartitioned");
     }
-    if (in.size() > 3) {
+    if (mha_is_packed(a)) {
+      require(in.size() > 3, a, "packed_sequences needs the segment lengths input");
+      auto const& l = in[3];
+      require(l.num_dims() == 2, a, "packed_sequences: segment lengths must be rank 2 [batch, M]");
+      require(is_integer_dtype(l.dtype), a, "packed_sequences: segment lengths must have an integer dtype");
+      require(l.sum_degree == 1, a, "packed_sequences: segment lengths cannot be a partial sum");
+      require(l.dim(0).degree == in[0].dim(0).degree, a,
+              "packed_sequences: segment lengths batch degree differs from q");
+      require(l.discard_copy_degree == in[0].discard_copy_degree, a,
+              "packed_sequences: segment lengths replica degree differs from q");
+      require(l.dim(1).degree == 1, a, "packed_sequences: the segment dim must be unpartitioned");
+      // a pack is self-contained, so packs shard over the batch; ring / Ulysses attention has no segments
+      require(in[0].dim(1).degree == 1 && in[1].dim(1).degree == 1 && in[2].dim(1).degree == 1, a,
+              "packed_sequences needs an unpartitioned sequence dim");
+    } else if (in.size() > 3) {
       auto const& l = in[3];
       require(l.num_dims() == 1, a, "key lengths must be rank 1 [batch]");
       require(is_integer_dtype(l.dtype), a, "key lengths must have an integer dtype");
@@ -1509,6 +1553,9 @@ OpWork estimate_op_work(const OpAttrs& a, const std::vector<TensorShape>& in,
       double b = static_cast<double>(in[0].dims[0]);
       double sq = static_cast<double>(in[0].dims[1]);
       double sk = static_cast<double>(in[1].dims[1]);
+      // packed sequences: a query sees at most max_seqlen keys, whatever the
+      // lengths are.  An upper bound: the real work is the sum of len^2
+      if (mha_is_packed(a)) sk = static_cast<double>(mha_max_seqlen(a, in[1].dims[1]));
       double h = static_cast<double>(w[0].dims[1]);  // local heads
       double p = static_cast<double>(w[0].dims[0]);
       double kd = a.i("kdim") > 0 ? static_cast<double>(a.i("kdim")) : static_cast<double>(a.i("embed_dim")) / static_cast<double>(a.i("num_heads"));

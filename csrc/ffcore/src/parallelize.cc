@@ -134,6 +134,10 @@ std::optional<std::vector<ParallelTensorShape>> required_input_shapes(const Comp
   if (op.type == OpType::MULTIHEAD_ATTENTION && ss.size() == 4 && cfg.batch > 1 && ss[3].num_dims() == 1 &&
       ss[3].dims[0] == ref.dims[0] && ss[3].dims[0] % cfg.batch == 0)
     ps[3] = lift_to_parallel_with_degrees(ss[3], 1, 1, {cfg.batch});
+  // packed sequences: the segment lengths [batch, M] shard with the packs and keep M whole
+  if (op.type == OpType::MULTIHEAD_ATTENTION && ss.size() == 4 && cfg.batch > 1 && ss[3].num_dims() == 2 &&
+      ss[3].dims[0] == ref.dims[0] && ss[3].dims[0] % cfg.batch == 0)
+    ps[3] = lift_to_parallel_with_degrees(ss[3], 1, 1, {cfg.batch, 1});
   // every requested degree must actually apply to input 0
   if (cfg.batch > 1 && (ref.num_dims() < 1 || ps[0].dim(0).degree != cfg.batch)) return std::nullopt;
   if (cfg.seq > 1 && (ref.num_dims() < 3 || ps[0].dim(attribute_dim(ref)).degree != cfg.seq)) return std::nullopt;

@@ -31,8 +31,10 @@
 //    workgroup per (batch, head), all three gradients from one S / dS.
 //
 // Kernels: attn_fwd_kernel, attn_bwd_dq_kernel and attn_bwd_dkdv_kernel, each
-// for D in {64, 128} x CAUSAL x DROP x VARLEN, and attn_bwd_onepass_kernel;
-// attention_fwd / attention_bwd pick one through with_head and with_features.
+// for D in {64, 128} x CAUSAL x DROP x VARLEN (and, with VARLEN, PACKED), and
+// attn_bwd_onepass_kernel; attention_fwd / attention_bwd pick one through
+// with_head and with_features.  Packed calls also launch
+// attn_segment_offsets_kernel (before) and attn_pack_tail_kernel (after).
 // Two environment switches: FFK_ATTN_PRIO (wave priority around the MFMA
 // clusters; default on at D = 128) and FFK_ATTN_BWD_ONEPASS (0: the kernel
 // pair where the one-pass kernel would run; read per call).
@@ -90,6 +92,33 @@
 // loop ends at the last live tile.  Either pointer may be null in a VARLEN
 // kernel: null means the physical extent.  The dropout hash index and the
 // dbias slab rows keep their physical positions.
+//
+// Packed sequences (PACKED instantiations, an axis of their own so that the
+// kernels of a call with lengths stay the code they were;
+// AttnTensors::seg_offsets, int32 [N, M, 2] on the device).  Row n of the
+// [N, T, H, D] tensors (a pack) holds up to M sequences (segments) end to end
+// from token 0; segment (n, m) is tokens start .. start + len of pack n, with
+// (start, len) written by attn_segment_offsets_kernel from seg_lens [N, M]
+// (start = sum of the pack's earlier clamped lengths, len clamped to
+// [0, min(max_seqlen, T - start)]) once per forward and kept for the backward.
+// A workgroup serves one segment: the grid's b is n * M + m over N * M * H
+// columns and ceil(max_seqlen / 128) blocks, Sq = Sk = max_seqlen, and the
+// segment's len takes the place of both lengths, so every rule above holds in
+// segment-local coordinates (causal and the dropout mask included: the hash
+// key is that of sample n * M + m, the row stride max_seqlen).  What differs:
+//  * every row address is pack base + (start + local row) * stride, and the
+//    LSE / delta words are [N, H, T] by physical token;
+//  * a dead row of one segment may be a live row of the next, so nothing is
+//    stored outside the segment: the dead-block exits store nothing (the
+//    dK/dV kernel has one too, ahead of its first barrier), the epilogues
+//    store live rows only, and the dK/dV zero stores for dead keys are off.
+//    Loaders bound rows by len, so a tile that straddles a segment end reads
+//    zeros for the neighbour's rows and leaves them untouched;
+//  * the tokens past a pack's last segment (the tail) are written by
+//    attn_pack_tail_kernel after the attention kernels: zeros in o / dQ / dK /
+//    dV and lse = -inf (the GEMMs around attention reduce over all T rows).
+// kv_lens / q_lens, dbias in either form, Sq != Sk and the one-pass backward
+// are not part of the packed mode (std::invalid_argument; always the pair).
 #include <cstdlib>
 #include <type_traits>
 
@@ -128,6 +157,9 @@ struct AttnParams {
   // per-sample lengths (VARLEN kernels only)
   const int32_t* kv_lens;   // [B]; keys >= kv_lens[b] of sample b do not exist
   const int32_t* q_lens;    // [B]; queries >= q_lens[b] of sample b do not exist
+  // packed sequences (PACKED kernels only; B = packs, Sq = Sk = max_seqlen)
+  const int32_t* seg_off;   // [B, M, 2]: clamped (start, len) of segment (n, m), from attn_segment_offsets_kernel
+  int M, T;                 // segment slots per pack; physical tokens per pack
 };
 
 // Row of register r of a 32 x 32 MFMA accumulator, before the lane half's
@@ -150,6 +182,27 @@ template <bool VARLEN>
 __device__ __forceinline__ int query_len(const AttnParams& P, int b) {
   if constexpr (VARLEN) return P.q_lens ? __builtin_amdgcn_readfirstlane(min(max(P.q_lens[b], 0), P.Sq)) : P.Sq;
   else return P.Sq;
+}
+
+// Packed sequences: the segment a workgroup serves.  `b` of the grid is the
+// segment n * M + m; its rows are tokens start .. start + len of pack n, and
+// the LSE / delta rows are [pack, head, physical token].  Both words are read
+// once per workgroup as scalars and clamped again, so that no content of the
+// offsets tensor can address outside the pack.
+struct Segment {
+  int n, start, len;
+};
+__device__ __forceinline__ Segment segment_of(const AttnParams& P, int b) {
+  const int st = min(max(__builtin_amdgcn_readfirstlane(P.seg_off[2 * b]), 0), P.T);
+  const int ln = min(max(__builtin_amdgcn_readfirstlane(P.seg_off[2 * b + 1]), 0), min(P.Sq, P.T - st));
+  return {b / P.M, st, ln};
+}
+// Index of a row's LSE / delta word.  `row` is the sample's row, or with
+// PACKED the physical token start + local row of pack pn.
+template <bool PACKED>
+__device__ __forceinline__ int64_t stat_index(const AttnParams& P, int bh, int pn, int hh, int row) {
+  if constexpr (PACKED) return (static_cast<int64_t>(pn) * P.H + hh) * P.T + row;
+  else return static_cast<int64_t>(bh) * P.Sq + row;
 }
 
 // A wave's 32 dead query rows (lane & 31 -> row, lane half h -> the row's odd
@@ -264,13 +317,15 @@ struct TileLoader {
   static constexpr int CHUNKS = ROWS * D / 8;
   static constexpr int PER = CHUNKS / NT;
   bf16x8 reg[PER];
-  __device__ __forceinline__ void load(const TensorView& t, int b, int h, int row0, int nrows) {
+  // rows row0 .. of a sample that has nrows; `base` is the sample's first
+  // physical row (a packed segment's start)
+  __device__ __forceinline__ void load(const TensorView& t, int b, int h, int row0, int nrows, int base = 0) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int c = threadIdx.x + NT * i;
       const int r = c / (D / 8), ch = c % (D / 8);
       if (row0 + r < nrows) {
-        reg[i] = *reinterpret_cast<const bf16x8*>(t.row(b, row0 + r, h) + ch * 8);
+        reg[i] = *reinterpret_cast<const bf16x8*>(t.row(b, base + row0 + r, h) + ch * 8);
       } else {
         reg[i] = bf16x8{};
       }
@@ -333,7 +388,7 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 // DROP: the dropped probabilities are zeroed after the row sum is taken, so
 // m, l and the LSE are those of the undropped softmax; the keep scale is
 // folded into the epilogue's 1 / l.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED>
 __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   constexpr int KS = D / 16;        // k-steps over the head dim
   constexpr int DT = D / 32;        // 32-wide output tiles over the head dim
@@ -348,19 +403,28 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;
   if (!CAUSAL) attn_head_block(bh, qb);
   const int b = bh / P.H, hh = bh % P.H;
+  // packed: b is a segment; its rows are ps .. ps + plen of pack pn
+  [[maybe_unused]] int pn = b, ps = 0, plen = 0;
+  if constexpr (PACKED) {
+    const Segment sg = segment_of(P, b);
+    pn = sg.n, ps = sg.start, plen = sg.len;
+  }
   const int q_blk = qb * 128;
   const int qw = q_blk + wave * 32;
   const int q = qw + (lane & 31);
-  const bool q_ok = q < P.Sq;
-  const int Skl = key_len<VARLEN>(P, b);  // keys of this sample
+  const bool q_ok = PACKED ? q < plen : q < P.Sq;  // packed: only a segment's own rows are written
+  const int Skl = PACKED ? plen : key_len<VARLEN>(P, b);  // keys of this sample
   // queries of this sample: q_live rows exist, q_ok rows have an output row
-  [[maybe_unused]] const int Sql = query_len<VARLEN>(P, b);
+  [[maybe_unused]] const int Sql = PACKED ? plen : query_len<VARLEN>(P, b);
   const bool q_live = VARLEN ? q < Sql : q_ok;
   if constexpr (VARLEN) {
     if (q_blk >= Sql) {  // a wholly dead block: o = 0, lse = -inf, no tile loop
-      if (q_ok) {
-        store_zero_rows<D>(P.o_out.row(b, q, hh), h);
-        if (h == 0) P.lse[static_cast<int64_t>(bh) * P.Sq + q] = -INFINITY;
+      // packed: nothing is stored, the rows belong to the next segment or the tail
+      if constexpr (!PACKED) {
+        if (q_ok) {
+          store_zero_rows<D>(P.o_out.row(b, q, hh), h);
+          if (h == 0) P.lse[static_cast<int64_t>(bh) * P.Sq + q] = -INFINITY;
+        }
       }
       return;
     }
@@ -370,7 +434,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   bf16x8 qf[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks)
-    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.row(b, q, hh) + ks * 16 + 8 * h) : bf16x8{};
+    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.row(pn, ps + q, hh) + ks * 16 + 8 * h) : bf16x8{};
 
   f32x16 o[DT];
 #pragma unroll
@@ -387,8 +451,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, b, hh, 0, Skl);
-  vl.load(P.v, b, hh, 0, Skl);
+  kl.load(P.k, pn, hh, 0, Skl, ps);
+  vl.load(P.v, pn, hh, 0, Skl, ps);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -400,8 +464,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
     if (__builtin_amdgcn_readfirstlane(qw) >= Sql) {
       for (int t = 0; t < n_tiles; ++t) {
         if (t + 1 < n_tiles) {
-          kl.load(P.k, b, hh, (t + 1) * KV, Skl);
-          vl.load(P.v, b, hh, (t + 1) * KV, Skl);
+          kl.load(P.k, pn, hh, (t + 1) * KV, Skl, ps);
+          vl.load(P.v, pn, hh, (t + 1) * KV, Skl, ps);
           unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
           kl.store(nxt);
           vl.store(nxt + TILE_BYTES);
@@ -417,8 +481,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
     if (has_next) {  // issue next tile's HBM loads before this tile's MFMAs
-      kl.load(P.k, b, hh, k0 + KV, Skl);
-      vl.load(P.v, b, hh, k0 + KV, Skl);
+      kl.load(P.k, pn, hh, k0 + KV, Skl, ps);
+      vl.load(P.v, pn, hh, k0 + KV, Skl, ps);
     }
     const bool wave_active = !CAUSAL || (k0 <= qw + 31);
     if (wave_active) {
@@ -525,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   }
   float inv = lt > 0.f ? 1.f / lt : 0.f;
   if constexpr (DROP) inv *= P.drop_rs;
-  store_rows16<DT>(P.o_out.row(b, q, hh), o, inv, h, q_ok);
+  store_rows16<DT>(P.o_out.row(pn, ps + q, hh), o, inv, h, q_ok);
   // VARLEN: the LSE index is formed here from an opaque copy of the row.  The
   // dead-block exit above forms the same 64-bit index, and as one value it
   // was hoisted above the tile loop and spilled across it (non-causal D = 128
@@ -533,7 +597,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
   int ql = q;
   if constexpr (VARLEN) asm volatile("" : "+v"(ql));
   if (q_ok && h == 0)
-    P.lse[static_cast<int64_t>(bh) * P.Sq + ql] = (lt > 0.f) ? m * P.scale_log2 + log2f(lt) : -INFINITY;
+    P.lse[stat_index<PACKED>(P, bh, pn, hh, ps + ql)] = (lt > 0.f) ? m * P.scale_log2 + log2f(lt) : -INFINITY;
 }
 
 // ===========================================================================
@@ -561,7 +625,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 // accumulates bq^T = K^T P^T from the K^T fragments of the dQ product (one
 // more MFMA product, DT more accumulators), and the epilogue adds
 // (dlt - delta) bq^T to dQ^T and writes delta for the dK / dV kernel.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED>
 __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, KV = 64;
   constexpr int TILE_BYTES = KV * D * 2;
@@ -571,20 +635,29 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;   // causal: longest-first (fwd)
   if (!CAUSAL) attn_head_block(bh, qb);
   const int b = bh / P.H, hh = bh % P.H;
+  // packed: b is a segment; its rows are ps .. ps + plen of pack pn
+  [[maybe_unused]] int pn = b, ps = 0, plen = 0;
+  if constexpr (PACKED) {
+    const Segment sg = segment_of(P, b);
+    pn = sg.n, ps = sg.start, plen = sg.len;
+  }
   const int q_blk = qb * 128;
   const int qw = q_blk + wave * 32;
   const int q = qw + (lane & 31);
-  const bool q_ok = q < P.Sq;
-  const int Skl = key_len<VARLEN>(P, b);  // keys of this sample
+  const bool q_ok = PACKED ? q < plen : q < P.Sq;  // packed: only a segment's own rows are written
+  const int Skl = PACKED ? plen : key_len<VARLEN>(P, b);  // keys of this sample
   // queries of this sample: q_live rows exist, q_ok rows have a dQ row
-  [[maybe_unused]] const int Sql = query_len<VARLEN>(P, b);
+  [[maybe_unused]] const int Sql = PACKED ? plen : query_len<VARLEN>(P, b);
   const bool q_live = VARLEN ? q < Sql : q_ok;
   if constexpr (VARLEN) {
     if (q_blk >= Sql) {  // a wholly dead block: dQ = 0 and zero dbias partials, no tile loop
-      if (q_ok) store_zero_rows<D>(P.dq.row(b, q, hh), h);
-      if (P.dbq && P.db_ld && qw < P.Sq) {
-        float* drow = P.dbq + (static_cast<int64_t>(b) * ((P.Sq + 31) / 32) + qw / 32) * P.db_ld + hh * D;
-        for (int c = lane; c < D; c += 64) drow[c] = 0.f;
+      // packed: nothing is stored, the rows belong to the next segment or the tail
+      if constexpr (!PACKED) {
+        if (q_ok) store_zero_rows<D>(P.dq.row(b, q, hh), h);
+        if (P.dbq && P.db_ld && qw < P.Sq) {
+          float* drow = P.dbq + (static_cast<int64_t>(b) * ((P.Sq + 31) / 32) + qw / 32) * P.db_ld + hh * D;
+          for (int c = lane; c < D; c += 64) drow[c] = 0.f;
+        }
       }
       return;
     }
@@ -593,24 +666,24 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   bf16x8 qf[KS], df[KS];
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.row(b, q, hh) + ks * 16 + 8 * h) : bf16x8{};
-    df[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.dout.row(b, q, hh) + ks * 16 + 8 * h) : bf16x8{};
+    qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.row(pn, ps + q, hh) + ks * 16 + 8 * h) : bf16x8{};
+    df[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.dout.row(pn, ps + q, hh) + ks * 16 + 8 * h) : bf16x8{};
   }
-  const float lse = q_live ? P.lse[static_cast<int64_t>(bh) * P.Sq + q] : 0.f;
+  const float lse = q_live ? P.lse[stat_index<PACKED>(P, bh, pn, hh, ps + q)] : 0.f;
   // lane (q, h) holds d = 16 ks + 8 h .. +8 of dO row q: a partial dot over
   // those, then the other half from lane ^ 32
   float part = 0.f;
   if (q_live) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      const bf16x8 of = *reinterpret_cast<const bf16x8*>(P.o.row(b, q, hh) + ks * 16 + 8 * h);
+      const bf16x8 of = *reinterpret_cast<const bf16x8*>(P.o.row(pn, ps + q, hh) + ks * 16 + 8 * h);
 #pragma unroll
       for (int e = 0; e < 8; ++e) part += bf2f(of[e]) * bf2f(df[ks][e]);
     }
   }
   const float dlt = part + __shfl_xor(part, 32, 64);
   if constexpr (!XDELTA)  // XDELTA writes the exact delta after the loop
-    if (q_live && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = dlt;
+    if (q_live && h == 0) P.delta[stat_index<PACKED>(P, bh, pn, hh, ps + q)] = dlt;
 
   f32x16 dq[DT];
 #pragma unroll
@@ -641,8 +714,8 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, b, hh, 0, Skl);
-  vl.load(P.v, b, hh, 0, Skl);
+  kl.load(P.k, pn, hh, 0, Skl, ps);
+  vl.load(P.v, pn, hh, 0, Skl, ps);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -661,8 +734,8 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     if (__builtin_amdgcn_readfirstlane(qw) >= Sql) {
       for (int t = 0; t < n_tiles; ++t) {
         if (t + 1 < n_tiles) {
-          kl.load(P.k, b, hh, (t + 1) * KV, Skl);
-          vl.load(P.v, b, hh, (t + 1) * KV, Skl);
+          kl.load(P.k, pn, hh, (t + 1) * KV, Skl, ps);
+          vl.load(P.v, pn, hh, (t + 1) * KV, Skl, ps);
           unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
           kl.store(nxt);
           vl.store(nxt + TILE_BYTES);
@@ -679,8 +752,8 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
     if (has_next) {
-      kl.load(P.k, b, hh, k0 + KV, Skl);
-      vl.load(P.v, b, hh, k0 + KV, Skl);
+      kl.load(P.k, pn, hh, k0 + KV, Skl, ps);
+      vl.load(P.v, pn, hh, k0 + KV, Skl, ps);
     }
     const bool wave_active = !CAUSAL || (k0 <= qw + 31);
     const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= (VARLEN ? Sql : P.Sq));
@@ -759,7 +832,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) dq[dt][r] = fmaf(c, bq[dt][r], dq[dt][r]);
-    if (q_live && h == 0) P.delta[static_cast<int64_t>(bh) * P.Sq + q] = delta;
+    if (q_live && h == 0) P.delta[stat_index<PACKED>(P, bh, pn, hh, ps + q)] = delta;
   }
   if (P.dbq && P.db_ld) {
     if (qw < P.Sq)  // waves wholly past the sequence own no slab row
@@ -768,7 +841,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
   } else if (P.dbq) {
     bias_colsum<DT>(dq, P.scale, P.dbq + hh * D, lane);
   }
-  store_rows16<DT>(P.dq.row(b, q, hh), dq, P.scale, h, q_ok);
+  store_rows16<DT>(P.dq.row(pn, ps + q, hh), dq, P.scale, h, q_ok);
 }
 
 // ===========================================================================
@@ -779,7 +852,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
 // hash index q * Sk + key steps by Sk per register; the dP accumulator starts
 // from zero and -delta is added after the keep scale (dS = P (keep rs dP -
 // delta)); dV takes keep . P and rs at the store.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED>
 __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32;
   // prefetched LDS fragments (below): GPT causal shape 0.341 -> 0.333 ms, BERT
@@ -797,13 +870,26 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
   if (!CAUSAL) attn_head_block(bh, kb);
   const int b = bh / P.H, hh = bh % P.H;
   const int k_blk = kb * (4 * KW);
+  // packed: b is a segment; its rows are ps .. ps + plen of pack pn.  Held as
+  // constants (and fetch_scalars below keeps its index form per mode): as
+  // mutable locals captured by the lambdas they changed the register
+  // allocation of every form without packing, which are to stay the code
+  // they were
+  Segment sg{b, 0, 0};
+  if constexpr (PACKED) sg = segment_of(P, b);
+  [[maybe_unused]] const int pn = sg.n, ps = sg.start, plen = sg.len;
+  // packed: a key block past the segment's end leaves here, ahead of the
+  // first barrier, and stores nothing (its rows are the next segment's)
+  if constexpr (PACKED) {
+    if (k_blk >= plen) return;
+  }
   const int kw = k_blk + wave * KW;
   // keys of this sample.  Without lengths every use reads P.Sk in place, as
   // it did before the kernel had lengths: held in a local, the causal forms
   // compiled to another instruction stream (3294 against 3305 instructions at
   // D = 64), and a call without lengths is to run the code it ran before
   [[maybe_unused]] int len_v = 0;
-  if constexpr (VARLEN) len_v = key_len<true>(P, b);
+  if constexpr (VARLEN) len_v = PACKED ? plen : key_len<true>(P, b);
   auto Skl = [&]() -> int {
     if constexpr (VARLEN) return len_v;
     else return P.Sk;
@@ -811,7 +897,7 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
   // queries of this sample, the same way: every bound on the query axis (the
   // tile count, the tile loads, the parked -lse / c, the masks) takes it
   [[maybe_unused]] int qlen_v = 0;
-  if constexpr (VARLEN) qlen_v = query_len<true>(P, b);
+  if constexpr (VARLEN) qlen_v = PACKED ? plen : query_len<true>(P, b);
   auto Sql = [&]() -> int {
     if constexpr (VARLEN) return qlen_v;
     else return P.Sq;
@@ -821,11 +907,12 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
   bf16x8 kf[KS], vf[KS];
   const int key = kw + (lane & 31);
   const bool k_ok = key < Skl();                    // the key exists (VARLEN: below the sample's length)
-  const bool k_st = VARLEN ? key < P.Sk : k_ok;     // the key has a dK / dV row to write (below the physical Sk)
+  // the key has a dK / dV row to write: below the physical Sk; packed, only the segment's own keys
+  const bool k_st = (VARLEN && !PACKED) ? key < P.Sk : k_ok;
 #pragma unroll
   for (int ks = 0; ks < KS; ++ks) {
-    kf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.k.row(b, key, hh) + ks * 16 + 8 * h) : bf16x8{};
-    vf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.v.row(b, key, hh) + ks * 16 + 8 * h) : bf16x8{};
+    kf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.k.row(pn, ps + key, hh) + ks * 16 + 8 * h) : bf16x8{};
+    vf[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.v.row(pn, ps + key, hh) + ks * 16 + 8 * h) : bf16x8{};
   }
   f32x16 dk[DT], dv[DT];
 #pragma unroll
@@ -864,9 +951,16 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
     // the causal VARLEN = false forms, which are to stay the code they were
     if constexpr (VARLEN) nok = threadIdx.x < QT && qq < qlen_v;
     else nok = threadIdx.x < QT && qq < P.Sq;
-    if (nok) {
-      nls = P.lse[static_cast<int64_t>(bh) * P.Sq + qq];
-      nds = P.delta[static_cast<int64_t>(bh) * P.Sq + qq];
+    if constexpr (PACKED) {
+      if (nok) {
+        nls = P.lse[stat_index<true>(P, bh, pn, hh, ps + qq)];
+        nds = P.delta[stat_index<true>(P, bh, pn, hh, ps + qq)];
+      }
+    } else {
+      if (nok) {
+        nls = P.lse[static_cast<int64_t>(bh) * P.Sq + qq];
+        nds = P.delta[static_cast<int64_t>(bh) * P.Sq + qq];
+      }
     }
   };
   auto park_scalars = [&](unsigned char* stage) {
@@ -882,8 +976,8 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
   // vmcnt(0), so the first MFMA of EVERY iteration waited on vmcnt — and
   // vmcnt retires in order, so that wait drained the next tile's prefetch
   // right after issuing it (one exposed global-load latency per tile)
-  ql.load(P.q, b, hh, t0 * QT, Sql());
-  dl.load(P.dout, b, hh, t0 * QT, Sql());
+  ql.load(P.q, pn, hh, t0 * QT, Sql(), ps);
+  dl.load(P.dout, pn, hh, t0 * QT, Sql(), ps);
   fetch_scalars(t0 * QT);
   ql.store(smem);
   dl.store(smem + TILE_BYTES);
@@ -899,8 +993,8 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
     const float* ds = ls + QT;
     const bool has_next = t + 1 < n_q_tiles;
     if (has_next) {
-      ql.load(P.q, b, hh, q0 + QT, Sql());
-      dl.load(P.dout, b, hh, q0 + QT, Sql());
+      ql.load(P.q, pn, hh, q0 + QT, Sql(), ps);
+      dl.load(P.dout, pn, hh, q0 + QT, Sql(), ps);
       fetch_scalars(q0 + QT);
     }
     const bool wave_active = !CAUSAL || (q0 + QT - 1 >= kw);
@@ -1033,8 +1127,8 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
     if (P.dbv) bias_colsum<DT>(dv, vmul, P.dbv + hh * D, lane);
   }
   // every lane swaps; k_st guards the stores
-  store_rows16<DT>(P.dk.row(b, key, hh), dk, P.scale, h, k_st);
-  store_rows16<DT>(P.dv.row(b, key, hh), dv, vmul, h, k_st);
+  store_rows16<DT>(P.dk.row(pn, ps + key, hh), dk, P.scale, h, k_st);
+  store_rows16<DT>(P.dv.row(pn, ps + key, hh), dv, vmul, h, k_st);
 }
 
 // ===========================================================================
@@ -1310,7 +1404,74 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_onepass_kernel(AttnParams P, 
 }
 
 // ===========================================================================
-static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale) {
+// Packed sequences: the two small kernels around the attention kernels.
+//
+// (start, len) of every segment from seg_lens [N, M]: one thread per pack
+// scans its M slots.  start is the sum of the earlier clamped lengths, len is
+// clamped to [0, min(max_seqlen, T - start)], so an over-full or negative row
+// of seg_lens still describes segments inside the pack.
+__global__ void attn_segment_offsets_kernel(const int32_t* __restrict__ seg_lens, int32_t* __restrict__ seg_off, int N,
+                                            int M, int T, int max_seqlen) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  int start = 0;
+  for (int m = 0; m < M; ++m) {
+    const int64_t i = static_cast<int64_t>(n) * M + m;
+    const int len = min(max(seg_lens[i], 0), min(max_seqlen, T - start));
+    seg_off[2 * i] = start;
+    seg_off[2 * i + 1] = len;
+    start += len;
+  }
+}
+
+// The tail of every pack (tokens at or past the end of its last segment):
+// zero rows in up to three [N, T, H, D] outputs and lse = -inf.  No attention
+// workgroup writes them, and the GEMMs around attention reduce over all T rows.
+// Grid (ceil(T / 16), N): a block owns 16 tokens and leaves at once when they
+// are all inside segments.
+__global__ __launch_bounds__(256) void attn_pack_tail_kernel(OutView a, OutView b, OutView c, float* __restrict__ lse,
+                                                              const int32_t* __restrict__ seg_off, int M, int T, int H,
+                                                              int D) {
+  constexpr int ROWS = 16;
+  const int n = blockIdx.y, row0 = blockIdx.x * ROWS;
+  const int64_t last = (static_cast<int64_t>(n) * M + (M - 1)) * 2;
+  const int tail = min(max(seg_off[last] + seg_off[last + 1], 0), T);
+  if (row0 + ROWS <= tail) return;
+  const int cpr = H * (D / 8);  // 16-byte chunks per token
+  for (int i = threadIdx.x; i < ROWS * cpr; i += blockDim.x) {
+    const int r = row0 + i / cpr, ch = i % cpr, hh = ch / (D / 8), d = (ch % (D / 8)) * 8;
+    if (r < tail || r >= T) continue;
+    const u32x4t z = {0u, 0u, 0u, 0u};
+    if (a.p) *reinterpret_cast<u32x4t*>(a.row(n, r, hh) + d) = z;
+    if (b.p) *reinterpret_cast<u32x4t*>(b.row(n, r, hh) + d) = z;
+    if (c.p) *reinterpret_cast<u32x4t*>(c.row(n, r, hh) + d) = z;
+  }
+  if (lse) {
+    for (int i = threadIdx.x; i < ROWS * H; i += blockDim.x) {
+      const int r = row0 + i / H, hh = i % H;
+      if (r >= tail && r < T) lse[(static_cast<int64_t>(n) * H + hh) * T + r] = -INFINITY;
+    }
+  }
+}
+
+void attention_segment_offsets(const int32_t* seg_lens, int32_t* seg_off, int N, int M, int T, int max_seqlen,
+                               hipStream_t st) {
+  if (N <= 0 || M <= 0 || T <= 0 || max_seqlen < 1 || max_seqlen > T)
+    throw std::invalid_argument("attention: packed sequences need N, M, T > 0 and 1 <= max_seqlen <= T");
+  hipLaunchKernelGGL(attn_segment_offsets_kernel, dim3(static_cast<unsigned>((N + 63) / 64)), dim3(64), 0, st,
+                     seg_lens, seg_off, N, M, T, max_seqlen);
+  FFK_LAUNCH_CHECK("attention_segment_offsets");
+}
+
+static void launch_pack_tail(const AttnParams& P, OutView a, OutView b, OutView c, float* lse, int N, int D,
+                             hipStream_t st) {
+  hipLaunchKernelGGL(attn_pack_tail_kernel, dim3(static_cast<unsigned>((P.T + 15) / 16), static_cast<unsigned>(N)),
+                     dim3(256), 0, st, a, b, c, lse, P.seg_off, P.M, P.T, P.H, D);
+}
+
+// ===========================================================================
+static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale,
+                              bool causal_grid) {
   AttnParams P{};
   auto tv = [](const AttnTensors::T& x) {
     return TensorView{static_cast<const bf16*>(x.p), x.sb, x.ss, x.sh};
@@ -1355,6 +1516,22 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
   }
   P.kv_lens = t.kv_lens;
   P.q_lens = t.q_lens;
+  if (t.seg_offsets) {
+    // packed sequences: B packs of seg_T tokens, Sq = Sk = max_seqlen
+    if (t.kv_lens || t.q_lens)
+      throw std::invalid_argument("attention: packed sequences (seg_lens) exclude kv_lens / q_lens");
+    if (Sq != Sk)
+      throw std::invalid_argument("attention: packed sequences (seg_lens) are self-attention, Sq must equal Sk");
+    if (t.dbq || t.dbk || t.dbv)
+      throw std::invalid_argument("attention: packed sequences (seg_lens) do not take fused dbias");
+    if (t.seg_M < 1 || Sq < 1 || Sq > t.seg_T)
+      throw std::invalid_argument("attention: packed sequences need M >= 1 and 1 <= max_seqlen <= T");
+    if (static_cast<int64_t>(B) * t.seg_M * H > (causal_grid ? 2147483647ll : 65535ll))
+      throw std::invalid_argument("attention: packed sequences: N * M * H exceeds the grid");
+    P.seg_off = t.seg_offsets;
+    P.M = t.seg_M;
+    P.T = t.seg_T;
+  }
   return P;
 }
 
@@ -1383,16 +1560,26 @@ static void with_features(bool drop, bool varlen, F&& f) {
 
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st) {
-  AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
-  const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nbh = static_cast<unsigned>(B * H);
+  AttnParams P = make_params(t, B, H, Sq, Sk, D, scale, causal);
+  // packed: one workgroup column per segment slot, B * M * H of them
+  const bool packed = P.seg_off != nullptr;
+  const unsigned nq = static_cast<unsigned>((Sq + 127) / 128);
+  const unsigned nbh = static_cast<unsigned>(packed ? B * P.M * H : B * H);
   dim3 grid = causal ? dim3(nbh, nq) : dim3(nq, nbh), block(256);
   with_head(D, causal, [&](auto d, auto c) {
-    with_features(P.drop_thr != 0, P.kv_lens || P.q_lens, [&](auto dr, auto vl) {
+    with_features(P.drop_thr != 0, P.kv_lens || P.q_lens || packed, [&](auto dr, auto vl) {
       constexpr int DD = decltype(d)::value;
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
-      hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, VL>), grid, block, 0, st, P);
+      if constexpr (VL) {
+        if (packed) {
+          hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, true, true>), grid, block, 0, st, P);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, VL, false>), grid, block, 0, st, P);
     });
   });
+  if (packed) launch_pack_tail(P, P.o_out, OutView{}, OutView{}, P.lse, B, D, st);
   FFK_LAUNCH_CHECK("attention_fwd");
 }
 
@@ -1412,8 +1599,9 @@ int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal
 
 int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                   hipStream_t st, float* ws) {
-  AttnParams P = make_params(t, B, H, Sq, Sk, D, scale);
-  const bool drop = P.drop_thr != 0, varlen = P.kv_lens || P.q_lens;
+  AttnParams P = make_params(t, B, H, Sq, Sk, D, scale, causal);
+  const bool packed = P.seg_off != nullptr;
+  const bool drop = P.drop_thr != 0, varlen = P.kv_lens || P.q_lens || packed;
   // a second key block needs the workspace: callers that pass none keep the
   // two-kernel path
   if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv || drop || varlen) && (Sk <= 256 || ws)) {
@@ -1422,17 +1610,25 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
     return 1;
   }
   const unsigned nq = static_cast<unsigned>((Sq + 127) / 128), nk = static_cast<unsigned>((Sk + 127) / 128);
-  const unsigned nbh = static_cast<unsigned>(B * H);
+  const unsigned nbh = static_cast<unsigned>(packed ? B * P.M * H : B * H);
   dim3 gq = causal ? dim3(nbh, nq) : dim3(nq, nbh), gk = causal ? dim3(nbh, nk) : dim3(nk, nbh), block(256);
   // dQ first: it writes the delta that the dK / dV kernel reads
   with_head(D, causal, [&](auto d, auto c) {
     with_features(drop, varlen, [&](auto dr, auto vl) {
       constexpr int DD = decltype(d)::value;
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, VL>), gq, block, 0, st, P);
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, VL>), gk, block, 0, st, P);
+      if constexpr (VL) {
+        if (packed) {
+          hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, true, true>), gq, block, 0, st, P);
+          hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, true, true>), gk, block, 0, st, P);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, VL, false>), gq, block, 0, st, P);
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, VL, false>), gk, block, 0, st, P);
     });
   });
+  if (packed) launch_pack_tail(P, P.dq, P.dk, P.dv, nullptr, B, D, st);
   FFK_LAUNCH_CHECK("attention_bwd");
   return 0;
 }

@@ -26,6 +26,14 @@ static AttnTensors::T tview(const py::tuple& t) {
 }
 
 // attention dropout: threshold T = round(p * 2^24) (0 = off), keep scale 2^24 / (2^24 - T)
+// packed sequences: seg_off = int32 [B, M, 2] from attention_segment_offsets (0 = off), T tokens per pack
+static void set_packed(AttnTensors& t, uintptr_t seg_off, int seg_M, int seg_T) {
+  if (!seg_off) return;
+  t.seg_offsets = reinterpret_cast<const int32_t*>(seg_off);
+  t.seg_M = seg_M;
+  t.seg_T = seg_T;
+}
+
 static void set_dropout(AttnTensors& t, uint32_t drop_t, uint64_t seed, uintptr_t seed_dev) {
   if (!drop_t) return;
   if (drop_t >= (1u << 24)) throw std::invalid_argument("attention: dropout threshold must be below 2^24");
@@ -143,13 +151,15 @@ PYBIND11_MODULE(_ffkernels, m) {
   });
   m.def("attention_fwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, uintptr_t lse, int B, int H, int Sq,
                             int Sk, int D, float scale, bool causal, uintptr_t st, uint32_t drop_t, uint64_t seed,
-                            uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens) {
+                            uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens, uintptr_t seg_off, int seg_M,
+                            int seg_T) {
     AttnTensors t;
     t.q = tview(q);
     t.k = tview(k);
     t.v = tview(v);
     t.o = tview(o);
     t.lse = F(lse);
+    set_packed(t, seg_off, seg_M, seg_T);
     set_dropout(t, drop_t, seed, seed_dev);
     t.kv_lens = reinterpret_cast<const int32_t*>(kv_lens);
     t.q_lens = reinterpret_cast<const int32_t*>(q_lens);
@@ -157,13 +167,15 @@ PYBIND11_MODULE(_ffkernels, m) {
   }, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"), py::arg("B"), py::arg("H"),
         py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"),
         py::arg("drop_t") = 0, py::arg("seed") = 0, py::arg("seed_dev") = 0, py::arg("kv_lens") = 0,
-        py::arg("q_lens") = 0);
+        py::arg("q_lens") = 0, py::arg("seg_off") = 0, py::arg("seg_M") = 0, py::arg("seg_T") = 0);
   m.def("attention_bwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, py::tuple dout, py::tuple dq,
                             py::tuple dk, py::tuple dv, uintptr_t lse, uintptr_t delta, int B, int H, int Sq, int Sk,
                             int D, float scale, bool causal, uintptr_t st, uintptr_t dbq, uintptr_t dbk,
                             uintptr_t dbv, int64_t db_ld, uintptr_t ws, uint32_t drop_t, uint64_t seed,
-                            uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens) {
+                            uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens, uintptr_t seg_off, int seg_M,
+                            int seg_T) {
     AttnTensors t;
+    set_packed(t, seg_off, seg_M, seg_T);
     t.q = tview(q);
     t.k = tview(k);
     t.v = tview(v);
@@ -186,7 +198,13 @@ PYBIND11_MODULE(_ffkernels, m) {
         py::arg("dv"), py::arg("lse"), py::arg("delta"), py::arg("B"), py::arg("H"), py::arg("Sq"), py::arg("Sk"),
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"), py::arg("dbq") = 0, py::arg("dbk") = 0,
         py::arg("dbv") = 0, py::arg("db_ld") = 0, py::arg("ws") = 0, py::arg("drop_t") = 0, py::arg("seed") = 0,
-        py::arg("seed_dev") = 0, py::arg("kv_lens") = 0, py::arg("q_lens") = 0);
+        py::arg("seed_dev") = 0, py::arg("kv_lens") = 0, py::arg("q_lens") = 0, py::arg("seg_off") = 0,
+        py::arg("seg_M") = 0, py::arg("seg_T") = 0);
+  m.def("attention_segment_offsets", [](uintptr_t seg_lens, uintptr_t seg_off, int N, int M, int T, int max_seqlen,
+                                        uintptr_t st) {
+    attention_segment_offsets(reinterpret_cast<const int32_t*>(seg_lens), reinterpret_cast<int32_t*>(seg_off), N, M,
+                              T, max_seqlen, S(st));
+  });
   m.def("attention_bwd_workspace", &attention_bwd_workspace, py::arg("B"), py::arg("H"), py::arg("Sq"),
         py::arg("Sk"), py::arg("D"), py::arg("causal"), py::arg("dbias"), py::arg("varlen") = false);
   m.def("gemm", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre, int M, int N, int K,

@@ -115,7 +115,27 @@ struct AttnTensors {
   // of a call with key lengths (always the dQ + dK/dV pair); nullptr = every
   // sample has Sq queries.
   const int32_t* q_lens = nullptr;
+  // packed sequences: several sequences laid end to end in each row ("pack")
+  // of the [B, seg_T, H, D] tensors.  seg_offsets is int32 [B, seg_M, 2] on
+  // the device, the clamped (start, len) of every segment slot as written by
+  // attention_segment_offsets(); the call's Sq = Sk is max_seqlen, the longest
+  // segment served (1 .. seg_T).  Attention is self-attention inside each
+  // segment in segment-local coordinates (causal and the dropout mask too:
+  // segment (n, m) draws the mask of sample n * seg_M + m of a [B * seg_M,
+  // max_seqlen] batch).  A workgroup serves one segment and writes only its
+  // rows; the rows past a pack's last segment are written as zeros (o, dq,
+  // dk, dv) and lse = -inf by a small launch of their own.  lse / delta are
+  // [B, H, seg_T].  Always the dQ + dK/dV kernel pair; excludes kv_lens,
+  // q_lens, dbias and Sq != Sk (std::invalid_argument).
+  const int32_t* seg_offsets = nullptr;
+  int seg_M = 0;
+  int seg_T = 0;
 };
+// seg_lens int32 [N, M] -> seg_off int32 [N, M, 2], both on the device: start =
+// sum of the pack's earlier clamped lengths, len clamped to [0, min(max_seqlen,
+// T - start)].
+void attention_segment_offsets(const int32_t* seg_lens, int32_t* seg_off, int N, int M, int T, int max_seqlen,
+                               hipStream_t st);
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st);
 // Returns the path that ran: 1 = the one-pass kernel (D = 64, non-causal,

@@ -540,7 +540,8 @@ class FFModel:
 
     def multihead_attention(self, query, key, value, embed_dim, num_heads, kdim=0, vdim=0, dropout=0.0, bias=True,
                             add_bias_kv=False, add_zero_attn=False, kernel_initializer=None, causal=False, name=None,
-                            seq_parallel_mode="auto", key_lengths=None, query_lengths=False):
+                            seq_parallel_mode="auto", key_lengths=None, query_lengths=False, packed_sequences=None,
+                            max_seqlen=None):
         """``seq_parallel_mode`` selects the lowering when a strategy shards
         the sequence dim: "ulysses" (all-to-all), "ring" or "auto".
 
@@ -552,8 +553,31 @@ class FFModel:
         length (self-attention over a padded batch; query and key sequence
         extents must be equal).  Queries at or past it do not exist: the
         attention output there is the output bias, and the kernels skip them.
-        Exact for training when the loss ignores the padded positions."""
+        Exact for training when the loss ignores the padded positions.
+
+        ``packed_sequences``: optional ``DT_INT32`` tensor [batch, M].  Every
+        row ("pack") of ``query`` holds up to M sequences laid end to end
+        from token 0; the tensor gives their lengths (0: an empty slot), each
+        clamped to what is left of the pack and to ``max_seqlen`` (default:
+        the sequence extent).  Attention is self-attention inside each
+        sequence; the tokens after a pack's last sequence see nothing and get
+        the output bias.  Every other operator of the model then runs on the
+        dense [batch, T, E] tensors without padding in them.  Excludes
+        ``key_lengths`` / ``query_lengths``, cross-attention and the
+        sequence-parallel path."""
         inputs, extra = [query, key, value], {}
+        if packed_sequences is not None:
+            if key_lengths is not None or query_lengths:
+                raise ValueError("multihead_attention: packed_sequences excludes key_lengths / query_lengths")
+            if len(packed_sequences.dims) != 2:
+                raise ValueError("multihead_attention: packed_sequences must be a [batch, M] tensor, got dims "
+                                 f"{list(packed_sequences.dims)}")
+            inputs.append(packed_sequences)
+            extra["packed_sequences"] = int(packed_sequences.dims[1])
+            if max_seqlen is not None:
+                extra["max_seqlen"] = int(max_seqlen)
+        elif max_seqlen is not None:
+            raise ValueError("multihead_attention: max_seqlen needs packed_sequences")
         if query_lengths and key_lengths is None:
             raise ValueError("multihead_attention: query_lengths=True needs key_lengths (the tensor bounds both axes)")
         if key_lengths is not None:

@@ -456,8 +456,66 @@ def _attn_q_lens(q_lens, q):
     return q_lens.data_ptr()
 
 
+def attention_segment_offsets(seg_lens, T: int, max_seqlen: Optional[int] = None):
+    """Clamped (start, len) of every segment of a packed batch: int32
+    [N, M, 2] from ``seg_lens`` int32 [N, M], computed on the device (no host
+    synchronisation; a captured call follows the tensor).  Pack n holds its
+    segments end to end from token 0: start is the sum of the pack's earlier
+    clamped lengths and len is clamped to [0, min(max_seqlen, T - start)], so
+    an over-full row cannot describe tokens outside the pack."""
+    if not isinstance(seg_lens, torch.Tensor) or seg_lens.dtype != torch.int32:
+        raise ValueError("attention: seg_lens (packed sequences) must be an int32 tensor")
+    if seg_lens.dim() != 2 or seg_lens.shape[1] < 1:
+        raise ValueError(f"attention: seg_lens (packed sequences) must be [N, M], got {tuple(seg_lens.shape)}")
+    if not seg_lens.is_cuda or not seg_lens.is_contiguous():
+        raise ValueError("attention: seg_lens (packed sequences) must be a contiguous GPU tensor")
+    T = int(T)
+    max_seqlen = T if max_seqlen is None else int(max_seqlen)
+    if not 1 <= max_seqlen <= T:
+        raise ValueError(f"attention: packed sequences need 1 <= max_seqlen <= T, got {max_seqlen} and T = {T}")
+    N, M = seg_lens.shape
+    off = torch.empty(N, M, 2, device=seg_lens.device, dtype=torch.int32)
+    if N:
+        ext().attention_segment_offsets(seg_lens.data_ptr(), off.data_ptr(), N, M, T, max_seqlen, _stream())
+    return off
+
+
+def _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens, dbias=None):
+    """(offsets pointer, M, T, max_seqlen, offsets) of a packed attention call;
+    every combination that the packed mode does not serve is refused here."""
+    N, T, H, D = q.shape
+    if kv_lens is not None or q_lens is not None:
+        raise ValueError("attention: packed sequences (seg_lens) cannot be combined with kv_lens / q_lens")
+    if k.shape[1] != T or v.shape[1] != T:
+        raise ValueError("attention: packed sequences (seg_lens) are self-attention: q, k, v need equal sequence "
+                         "extents (cross-attention packs are not supported)")
+    if dbias is not None:
+        raise ValueError("attention: packed sequences (seg_lens) do not take the fused dbias (slab or atomic); "
+                         "sum the columns of dq / dk / dv instead")
+    if not isinstance(seg_lens, torch.Tensor) or seg_lens.dtype != torch.int32:
+        raise ValueError("attention: seg_lens (packed sequences) must be an int32 tensor")
+    if seg_lens.dim() != 2 or seg_lens.shape[0] != N or seg_lens.shape[1] < 1:
+        raise ValueError(f"attention: seg_lens (packed sequences) has shape {tuple(seg_lens.shape)}, expected "
+                         f"({N}, M)")
+    if seg_lens.device != q.device:
+        raise ValueError("attention: seg_lens (packed sequences) must be on the device of q")
+    M = int(seg_lens.shape[1])
+    if seg_offsets is None:
+        seg_offsets = attention_segment_offsets(seg_lens, T, max_seqlen)
+    elif (not isinstance(seg_offsets, torch.Tensor) or seg_offsets.dtype != torch.int32
+          or tuple(seg_offsets.shape) != (N, M, 2) or seg_offsets.device != q.device
+          or not seg_offsets.is_contiguous()):
+        raise ValueError(f"attention: seg_offsets (packed sequences) must be a contiguous int32 [{N}, {M}, 2] tensor "
+                         "on the device of q")
+    ms = T if max_seqlen is None else int(max_seqlen)
+    if not 1 <= ms <= T:
+        raise ValueError(f"attention: packed sequences need 1 <= max_seqlen <= T, got {ms} and T = {T}")
+    STATS["attention_packed"] += 1
+    return seg_offsets.data_ptr(), M, T, ms, seg_offsets
+
+
 def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None,
-                  q_lens=None):
+                  q_lens=None, seg_lens=None, max_seqlen=None, seg_offsets=None):
     """Flash attention forward.  q,k,v: [B, S, H, D] bf16 views (any b/s/h
     strides, e.g. slices of a packed [B, S, 3, H, D] QKV buffer).
     Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain).
@@ -479,11 +537,37 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     0 <= q_lens[b] <= Sq, with or without ``kv_lens``.  Queries >= q_lens[b] of
     sample b do not exist: their Q rows are never read, they are skipped in
     the kernels (whole 128-row blocks and 32-row waves do no attention work)
-    and o = 0, lse = -inf are stored for them."""
+    and o = 0, lse = -inf are stored for them.
+
+    ``seg_lens``: packed sequences.  An int32 [N, M] device tensor: row n of
+    q / k / v ([N, T, H, D]) holds up to M sequences ("segments") end to end
+    from token 0, of these lengths (0: an empty slot), each clamped to
+    [0, min(max_seqlen, T - start)] (``attention_segment_offsets``).
+    Attention is self-attention inside each segment, in segment-local
+    coordinates (``causal`` too); the dropout mask of segment (n, m) is that
+    of sample n * M + m of ``attention_dropout_mask(N * M, H, max_seqlen,
+    max_seqlen, ...)``.  Tokens past a pack's last segment get o = 0 and
+    lse = -inf and are never read.  ``max_seqlen`` (default T) bounds the
+    segment length and sizes the grid.  ``seg_offsets``: the result of
+    ``attention_segment_offsets`` for these arguments, if the caller already
+    has it.  Excludes ``kv_lens`` / ``q_lens`` and cross-attention."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     if D not in (64, 128):
         raise ValueError("attention: head dim must be 64 or 128")
+    if seg_lens is not None:
+        pk = _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens)
+        if k.shape != (B, Sk, H, D) or v.shape != (B, Sk, H, D):
+            raise ValueError("attention: q/k/v shape mismatch")
+        drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, pk[3], pk[3])
+        if out is None:
+            out = torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
+        lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
+        sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+        ext().attention_fwd(_view4(q), _view4(k), _view4(v), _view4(out), lse.data_ptr(), B, H, pk[3], pk[3], D, sc,
+                            bool(causal), _stream(), *drop, 0, 0, pk[0], pk[1], pk[2])
+        STATS["attention_fwd"] += 1
+        return out, lse
     if k.shape != (B, Sk, H, D) or v.shape != (B, Sk, H, D):
         raise ValueError("attention: q/k/v shape mismatch")
     drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
@@ -500,7 +584,8 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
 
 
 def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False,
-                  dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None, q_lens=None):
+                  dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None, q_lens=None, seg_lens=None, max_seqlen=None,
+                  seg_offsets=None):
     """Flash-attention backward into dq / dk / dv; returns the path that ran
     (1: the one-pass kernel, 0: the dQ and dK/dV kernels).  ``dropout_p``,
     ``seed``, ``seed_dev``: those of the forward call that produced ``o``
@@ -513,9 +598,16 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     column sums of dq / dk / dv (over batch and sequence) computed in the
     kernels' epilogues: by default each wave stores its 32-row partial into a
     slab that one reduction then adds (no atomics); ``dbias_atomic`` uses
-    per-column fp32 atomics instead (round 2's form, 2x slower kernels)."""
+    per-column fp32 atomics instead (round 2's form, 2x slower kernels).
+    ``seg_lens``, ``max_seqlen``, ``seg_offsets``: the forward call's packed
+    sequences (always path 0, no ``dbias``); every segment's rows of dq / dk /
+    dv are written by its own workgroups and the rows past a pack's last
+    segment as zeros."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
+    pk = None
+    if seg_lens is not None:
+        pk = _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens, dbias)
     for name, t, shp in (("o", o, (B, Sq, H, D)), ("do", do, (B, Sq, H, D)), ("dq", dq, (B, Sq, H, D)),
                          ("dk", dk, (B, Sk, H, D)), ("dv", dv, (B, Sk, H, D))):
         if tuple(t.shape) != shp:
@@ -539,6 +631,13 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
             dbs = [slab.data_ptr() + 4 * i * HD if t is not None else 0 for i, t in enumerate(dbias)]
     # the one-pass kernel (D = 64, non-causal, Sk <= 512, no dbias) keeps the
     # first key block's dQ in an fp32 scratch when there is a second one
+    if pk is not None:
+        drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, pk[3], pk[3])
+        ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
+                            _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, pk[3], pk[3], D, sc, bool(causal),
+                            _stream(), 0, 0, 0, 0, 0, *drop, 0, 0, pk[0], pk[1], pk[2])
+        STATS["attention_bwd"] += 1
+        return 0
     drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
     lens = _attn_kv_lens(kv_lens, q)
     qlens = _attn_q_lens(q_lens, q)

@@ -47,6 +47,15 @@ class BertConfig:
     # exist as queries either; every layer's attention skips them.  For
     # training with a loss that ignores the padded positions
     query_lengths: bool = False
+    # M > 0: packed sequences.  Every row of the [batch, sequence_length]
+    # inputs holds up to M sequences end to end, an int32 input `seg_lens`
+    # [batch, M] carries their lengths (0: an empty slot) and every layer's
+    # attention stays inside a sequence.  The data supplies position ids that
+    # restart per sequence and labels of -100 after a row's last sequence.
+    # max_seqlen (0: sequence_length) bounds a sequence's length.  Excludes
+    # key_lengths / query_lengths
+    packed_sequences: int = 0
+    max_seqlen: int = 0
 
     @property
     def padded_vocab(self) -> int:
@@ -93,12 +102,21 @@ def build_bert(model: FFModel, cfg: BertConfig) -> Tuple[Dict[str, object], obje
     if cfg.key_lengths:
         lens = model.create_tensor([B], DataType.DT_INT32, create_grad=False, name="seq_lens")
         inputs["seq_lens"] = lens
+    packed = {}
+    if cfg.packed_sequences:
+        if cfg.key_lengths or cfg.query_lengths:
+            raise ValueError("BertConfig: packed_sequences excludes key_lengths / query_lengths")
+        seg = model.create_tensor([B, cfg.packed_sequences], DataType.DT_INT32, create_grad=False, name="seg_lens")
+        inputs["seg_lens"] = seg
+        packed = dict(packed_sequences=seg, max_seqlen=cfg.max_seqlen or None)
+    elif cfg.max_seqlen:
+        raise ValueError("BertConfig: max_seqlen needs packed_sequences")
     act = ActiMode.AC_MODE_GELU if cfg.hidden_act == "gelu" else ActiMode.AC_MODE_RELU
     for i in range(cfg.num_encoder_layers):
         pre = f"encoder.{i}"
         a = model.multihead_attention(x, x, x, E, cfg.num_heads, dropout=cfg.attention_probs_dropout_prob,
                                       bias=True, kernel_initializer=proj_init, name=f"{pre}.attn", key_lengths=lens,
-                                      query_lengths=cfg.query_lengths)
+                                      query_lengths=cfg.query_lengths, **packed)
         if cfg.hidden_dropout_prob > 0:
             a = model.dropout(a, cfg.hidden_dropout_prob, i, name=f"{pre}.attn_dropout")
         x = model.layer_norm(model.add(a, x, name=f"{pre}.attn_residual"), [-1], True, cfg.layer_norm_eps,

@@ -30,6 +30,20 @@ lens[b] do not exist: their rows of q and of the incoming gradient are never
 read, o = 0 and dQ = 0 there, and they add nothing to dK / dV.  The kernels
 skip them, so the attention work of a sample follows lens[b]^2.  Exact when
 the loss ignores the padded positions (their incoming gradient is zero).
+
+Packed sequences (attribute ``packed_sequences`` = M; the fourth input is then
+an integer tensor [B, M]): every row ("pack") of the [B, T, E] input holds up
+to M sequences ("segments") end to end from token 0, of the given lengths
+(0: an empty slot).  Segment (n, m) occupies tokens [start, start + len) of
+pack n, start = the sum of the pack's earlier clamped lengths, len clamped to
+[0, min(max_seqlen, T - start)].  Attention is self-attention inside each
+segment in segment-local coordinates (query i sees keys 0 .. len - 1 of its
+segment, 0 .. i with ``causal``); the tokens after the last segment (the tail)
+see nothing and are seen by nothing: o = 0 and dQ = dK = dV = 0 there, and
+their content (NaN included) reaches no output.  The dropout mask of segment
+(n, m) is that of sample n * M + m of attention_dropout_mask(B * M, H,
+max_seqlen, max_seqlen, ...).  Every other operator of the model runs on the
+dense [B, T, E] tensors, which now hold no padding between sequences.
 """
 from __future__ import annotations
 
@@ -87,6 +101,57 @@ def _split_weights(W, E, Hl, kd, vd, Eq, Ek, Ev):
     o0 += Ev * Hl * vd
     Wo = flat[o0:o0 + Hl * vd * E].view(Hl * vd, E)
     return {"q": Wq, "k": Wk, "v": Wv, "o": Wo}
+
+
+def packed_segments(seg_lens, T, max_seqlen=None):
+    """(start, len) int64 [N, M] each, and the segment id of every token
+    int64 [N, T] (-1: the tail), of a packed batch: the definition that
+    kernels.attention_segment_offsets implements on the device."""
+    N, M = seg_lens.shape
+    ms = T if max_seqlen is None else int(max_seqlen)
+    start = torch.zeros(N, M, dtype=torch.int64, device=seg_lens.device)
+    lens = torch.zeros_like(start)
+    pos = torch.zeros(N, dtype=torch.int64, device=seg_lens.device)
+    for m in range(M):
+        ln = torch.minimum(seg_lens[:, m].to(torch.int64).clamp(0, ms), T - pos)
+        start[:, m], lens[:, m] = pos, ln
+        pos = pos + ln
+    tok = torch.arange(T, device=seg_lens.device).view(1, 1, T)
+    inside = (tok >= start[:, :, None]) & (tok < (start + lens)[:, :, None])            # [N, M, T]
+    seg_id = torch.where(inside.any(1), inside.to(torch.int64).argmax(1), torch.full_like(pos, -1)[:, None])
+    return start, lens, seg_id
+
+
+def _torch_packed_attention(q, k, v, causal, scale, seg_lens, max_seqlen=None, drop=None):
+    # q,k,v: [N, T, H, D]; seg_lens [N, M].  The block-diagonal (and causal) mask in physical coordinates;
+    # drop = (keep mask [N * M, H, max_seqlen, max_seqlen], keep scale) in segment-local coordinates
+    N, T, H, _ = q.shape
+    M = seg_lens.shape[1]
+    start, _, seg_id = packed_segments(seg_lens, T, max_seqlen)
+    tail = seg_id < 0                                                                   # [N, T]
+    # tail rows are never read: zeros in their place (0 * NaN), and no gradient flows into them
+    qt, kt, vt = (t.masked_fill(tail[:, :, None, None], 0).transpose(1, 2) for t in (q, k, v))
+    s = torch.matmul(qt.float(), kt.float().transpose(-1, -2)) * scale                  # [N, H, T, T]
+    see = (seg_id[:, :, None] == seg_id[:, None, :]) & ~tail[:, :, None]                # [N, Tq, Tk]
+    if causal:
+        see = see & ~torch.ones(T, T, dtype=torch.bool, device=s.device).triu(1)
+    s = s.masked_fill(~see[:, None], float("-inf"))
+    s = s.masked_fill(tail[:, None, :, None], 0.0)   # a tail row: finite scores for the softmax, zeroed below
+    p = torch.softmax(s, -1)
+    p = p.masked_fill(~see[:, None], 0.0)
+    if drop is not None:
+        keep, rs = drop
+        sid = seg_id.clamp(min=0)
+        loc = torch.arange(T, device=q.device).view(1, T) - torch.gather(start, 1, sid)   # local coordinate
+        ms = keep.shape[-1]
+        loc = loc.clamp(0, ms - 1)
+        smp = torch.arange(N, device=q.device).view(N, 1) * M + sid                       # sample n * M + m
+        kp = keep[smp[:, None, :, None], torch.arange(H, device=q.device).view(1, H, 1, 1),
+                  loc[:, None, :, None], loc[:, None, None, :]]                           # [N, H, T, T]
+        p = p * kp.to(p.dtype) * rs
+    o = torch.matmul(p, vt.float())
+    o = o.masked_fill(tail[:, None, :, None], 0)
+    return o.transpose(1, 2).to(q.dtype)
 
 
 def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=None):
@@ -312,7 +377,22 @@ class MultiHeadAttentionOp(OpImpl):
     def forward(self, ctx: OpContext, inputs, weights):
         q_in, k_in, v_in = inputs[:3]
         lens = None
-        if len(inputs) > 3:  # per-sample key lengths
+        # packed sequences: the fourth input is [B, M] segment lengths
+        M_pack = int(ctx.a("packed_sequences", 0) or 0)
+        seg = None
+        if M_pack:
+            if len(inputs) < 4:
+                raise ValueError(f"{ctx.name}: packed_sequences needs the segment lengths input")
+            seg = inputs[3]
+            if seg.dtype.is_floating_point or seg.dim() != 2 or tuple(seg.shape) != (q_in.shape[0], M_pack):
+                raise ValueError(f"{ctx.name}: packed_sequences: segment lengths must be an integer tensor "
+                                 f"[batch, {M_pack}], got {seg.dtype} {tuple(seg.shape)}")
+            if bool(ctx.a("key_lengths", False)) or bool(ctx.a("query_lengths", False)):
+                raise ValueError(f"{ctx.name}: packed_sequences excludes key_lengths / query_lengths")
+            if not (q_in is k_in and k_in is v_in) and not (q_in.shape[1] == k_in.shape[1] == v_in.shape[1]):
+                raise ValueError(f"{ctx.name}: packed_sequences needs equal q / k / v sequence extents")
+            seg = seg.to(torch.int32).contiguous()
+        elif len(inputs) > 3:  # per-sample key lengths
             lens = inputs[3].reshape(-1)
             if lens.dtype.is_floating_point or lens.shape[0] != q_in.shape[0]:
                 raise ValueError(f"{ctx.name}: key lengths must be an integer tensor [batch], got "
@@ -356,7 +436,12 @@ class MultiHeadAttentionOp(OpImpl):
         # the backward; the mask is attention_dropout_mask(seed + step word)
         p_drop = float(ctx.a("dropout", 0.0) or 0.0) if ctx.training else 0.0
         drop = None
+        max_seqlen = (int(ctx.a("max_seqlen", 0) or 0) or Sq) if seg is not None else None
+        seg_off = None
         if grp is not None and grp.size > 1:
+            if seg is not None:
+                raise NotImplementedError(f"{ctx.name}: packed sequences are not supported on the sequence-parallel "
+                                          "(ring / Ulysses) attention path")
             if lens is not None:
                 raise NotImplementedError(f"{ctx.name}: key lengths are not supported on the sequence-parallel "
                                           "(ring / Ulysses) attention path")
@@ -372,7 +457,16 @@ class MultiHeadAttentionOp(OpImpl):
         else:
             if p_drop > 0 and K.attention_dropout_threshold(p_drop):
                 drop = (p_drop, _drop_seed(ctx), _drop_step(ctx, q.device))
-            if use_flash:
+            if use_flash and seg is not None:
+                kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+                # once per forward, on the device; kept for the backward
+                seg_off = K.attention_segment_offsets(seg, Sq, max_seqlen)
+                o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale, seg_lens=seg, max_seqlen=max_seqlen,
+                                         seg_offsets=seg_off, **kw)
+            elif seg is not None:
+                o, lse = _torch_packed_attention(q, k, v, causal, scale, seg, max_seqlen,
+                                                 _fallback_mask(drop, B * M_pack, Hl, max_seqlen, max_seqlen)), None
+            elif use_flash:
                 kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
                 o, lse = K.attention_fwd(q, k, v, causal=causal, scale=scale, kv_lens=lens, q_lens=qlens, **kw)
             else:
@@ -381,12 +475,13 @@ class MultiHeadAttentionOp(OpImpl):
         o2 = o.reshape(B * Sq, Hl * vd)
         out = matmul(o2, ws["o"], bias=b_out)
         saved = (x2, k_in if not self_attn else None, v_in if not self_attn else None, proj, o, lse, ws,
-                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale), (lens, qlens), drop)
+                 self_attn, (B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale), (lens, qlens, seg, max_seqlen, seg_off),
+                 drop)
         return [out.view(B, Sq, E)], saved
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
-        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims, (lens, qlens), drop = saved
-        no_lens_grad = [None] if lens is not None else []   # the lengths input gets no gradient
+        x2, k_in, v_in, proj, o, lse, ws, self_attn, dims, (lens, qlens, seg, max_seqlen, seg_off), drop = saved
+        no_lens_grad = [None] if (lens is not None or seg is not None) else []   # the lengths input gets no gradient
         B, Sq, Sk, Hl, kd, vd, Eq, Ek, Ev, E, causal, scale = dims
         dW = weight_grads[0]
         db_in = weight_grads[1] if len(weight_grads) > 1 else None
@@ -432,19 +527,26 @@ class MultiHeadAttentionOp(OpImpl):
             else:
                 dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
             fused_db = None
-            if _FUSED_DBIAS and self_attn and db_in is not None and kd == vd \
+            # packed sequences: the column-sum pass below (tail rows of dQKV are zeros)
+            if _FUSED_DBIAS and seg is None and self_attn and db_in is not None and kd == vd \
                     and db_in.dtype == torch.float32 and db_in.is_contiguous():
                 dbf = db_in.reshape(-1)
                 n = Hl * kd
                 fused_db = (dbf[:n], dbf[n:2 * n], dbf[2 * n:3 * n])
             kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+            if seg is not None:
+                kw.update(seg_lens=seg, max_seqlen=max_seqlen, seg_offsets=seg_off)
             K.attention_bwd(q, k, v, o, lse, do4, dq, dk, dv, causal=causal, scale=scale, dbias=fused_db,
                             kv_lens=lens, q_lens=qlens, **kw)
             if fused_db is not None:
                 db_in = None   # accumulated by the attention backward kernels
         else:
             qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
-            ref = _torch_attention(qf, kf, vf, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens, qlens)
+            if seg is not None:
+                ref = _torch_packed_attention(qf, kf, vf, causal, scale, seg, max_seqlen,
+                                              _fallback_mask(drop, B * seg.shape[1], Hl, max_seqlen, max_seqlen))
+            else:
+                ref = _torch_attention(qf, kf, vf, causal, scale, _fallback_mask(drop, B, Hl, Sq, Sk), lens, qlens)
             ref.float().backward(do4.float())
             dq, dk, dv = (t.grad.to(do.dtype) for t in (qf, kf, vf))
             if self_attn:

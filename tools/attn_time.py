@@ -8,6 +8,7 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
     python tools/attn_time.py --dropout 0.1                           (attention dropout against p = 0)
     python tools/attn_time.py --varlen [--dropout 0.1]                (per-sample key lengths against full length)
     python tools/attn_time.py --varlen --queries [--dropout 0.1]      (the same lengths as query lengths too)
+    python tools/attn_time.py --packed [--dropout 0.1]                (packed sequences against the padded batch)
 
 --d128 appends two D = 128 shapes to whichever mode is run.
 """
@@ -184,7 +185,74 @@ def varlen_ab(iters, rounds=5, seed=0, p=0.0, queries=False):
         print(json.dumps(rec), flush=True)
 
 
+def first_fit(lens, T):
+    """Sequences of these lengths packed first-fit into rows of T tokens:
+    a list of rows, each the list of its sequences' indices."""
+    rows, room = [], []
+    for i, n in enumerate(lens):
+        for r in range(len(rows)):
+            if room[r] >= n:
+                rows[r].append(i)
+                room[r] -= n
+                break
+        else:
+            rows.append([i])
+            room.append(T - n)
+    return rows
+
+
+def packed_ab(iters, rounds=5, seed=0, p=0.0):
+    """Interleaved same-process timing of the forward and the backward over B
+    sequences of lengths uniform in [S / 8, S] (fixed seed), padded ([B, S]
+    with kv_lens = q_lens = lens) against packed first-fit into rows of T = S
+    tokens ([N, S] with seg_lens [N, M], M the most sequences of a row).
+    `exit_padded` / `exit_packed` are the shares of forward workgroups that
+    leave at once (their 128-query block is past the sample's or segment's
+    length); `tokens_padded` / `tokens_packed` the tokens the rest of a model
+    would run over."""
+    import statistics
+    for name, (B, S, H, D, causal) in SHAPES.items():
+        g = torch.Generator(device="cuda").manual_seed(0)
+        lens = torch.randint(S // 8, S + 1, (B,), generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
+        ll = lens.tolist()
+        rows = first_fit(ll, S)
+        N, M = len(rows), max(len(r) for r in rows)
+        seg = torch.zeros(N, M, dtype=torch.int32)
+        for n, r in enumerate(rows):
+            seg[n, :len(r)] = torch.tensor([ll[i] for i in r], dtype=torch.int32)
+        nq = (S + 127) // 128
+        dead_pad = sum(1 for n in ll for qb in range(nq) if qb * 128 >= n)
+        dead_pack = sum(1 for n in seg.reshape(-1).tolist() for qb in range(nq) if qb * 128 >= n)
+        t = {}
+        for tag, rows_n, kw in (("padded", B, dict(kv_lens=lens.cuda(), q_lens=lens.cuda())),
+                                ("packed", N, dict(seg_lens=seg.cuda(), max_seqlen=S))):
+            qkv = torch.randn(rows_n, S, 3, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+            do = torch.randn(rows_n, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+            t[tag] = dict(qkv=qkv, do=do, d=torch.empty_like(qkv), kw=dict(kw, causal=causal, dropout_p=p, seed=1234),
+                          fwd=[], bwd=[])
+        for _ in range(rounds):
+            for tag, c in t.items():
+                q, k, v = c["qkv"][:, :, 0], c["qkv"][:, :, 1], c["qkv"][:, :, 2]
+                d, kw = c["d"], c["kw"]
+                if "seg_lens" in kw:   # as the operator does: the offsets once per forward, kept for the backward
+                    kw = dict(kw, seg_offsets=K.attention_segment_offsets(kw["seg_lens"], S, S))
+                o, lse = K.attention_fwd(q, k, v, **c["kw"])
+                c["fwd"].append(_time(lambda: K.attention_fwd(q, k, v, out=o, **c["kw"]), iters))
+                c["bwd"].append(_time(lambda: K.attention_bwd(q, k, v, o, lse, c["do"], d[:, :, 0], d[:, :, 1],
+                                                              d[:, :, 2], **kw), iters))
+        rec = {"shape": name, "seed": seed, "dropout": p, "sequences": B, "mean_len": round(float(lens.float().mean()), 1),
+               "packs": N, "M": M, "tokens_padded": B * S, "tokens_packed": N * S, "tokens_live": int(lens.sum()),
+               "exit_padded": round(dead_pad / (B * nq), 4), "exit_packed": round(dead_pack / (N * M * nq), 4)}
+        for which in ("fwd", "bwd"):
+            for tag, c in t.items():
+                rec[f"{which}_ms_{tag}"] = round(statistics.median(c[which]), 4)
+                rec[f"{which}_rounds_{tag}"] = [round(x, 4) for x in c[which]]
+        print(json.dumps(rec), flush=True)
+
+
 def main():
+    if "--packed" in sys.argv:         # packed sequences against the padded batch with key and query lengths
+        return packed_ab(30, p=float(sys.argv[sys.argv.index("--dropout") + 1]) if "--dropout" in sys.argv else 0.0)
     if "--varlen" in sys.argv:         # per-sample key lengths against full length
         return varlen_ab(30, p=float(sys.argv[sys.argv.index("--dropout") + 1]) if "--dropout" in sys.argv else 0.0,
                          queries="--queries" in sys.argv)
