@@ -82,6 +82,11 @@ class ComputationGraph {
   ValueRef multihead_attention(ValueRef q, ValueRef k, ValueRef v, int64_t embed_dim, int64_t num_heads,
                                int64_t kdim = 0, int64_t vdim = 0, double dropout = 0.0,
                                bool bias = true, bool causal = false, const std::string& name = "");
+  // q [B, H, Sq, D], k / v [B, H, Sk, D], optional additive float mask broadcastable to [B, H, Sq, Sk];
+  // scale 0 = 1 / sqrt(D)
+  ValueRef scaled_dot_product_attention(ValueRef q, ValueRef k, ValueRef v, std::optional<ValueRef> mask = {},
+                                        bool causal = false, double dropout = 0.0, double scale = 0.0,
+                                        const std::string& name = "");
   ValueRef layer_norm(ValueRef x, const std::vector<int64_t>& axes, bool affine = true, double eps = 1e-5,
                       const std::string& name = "");
   ValueRef batch_norm(ValueRef x, bool relu = true, const std::string& name = "");

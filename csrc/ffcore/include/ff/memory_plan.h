@@ -67,6 +67,8 @@ struct MemoryPlanConfig {
   //  * LINEAR with an activation keeps its pre-activation too (x2);
   //  * MULTIHEAD_ATTENTION keeps the q / k / v projections and the
   //    attention output (flash attention: no score matrix) beside its output;
+  //  * SDPA keeps its inputs (q, k, v and the mask, where one is given), its
+  //    output and the fp32 LSE; no Sq x Sk buffer;
   //  * an output that neither its producer's nor any consumer's backward
   //    reads is freed after its last forward reader (the executor drops it
   //    from its environment); otherwise it lives until its last reader's

@@ -135,6 +135,16 @@ ValueRef ComputationGraph::multihead_attention(ValueRef q, ValueRef k, ValueRef 
   return add_layer(a, {q, k, v}, name)[0];
 }
 
+ValueRef ComputationGraph::scaled_dot_product_attention(ValueRef q, ValueRef k, ValueRef v,
+                                                        std::optional<ValueRef> mask, bool causal, double dropout,
+                                                        double scale, const std::string& name) {
+  OpAttrs a(OpType::SDPA);
+  a.set("causal", causal).set("dropout", dropout).set("scale", scale).set("mask", mask.has_value());
+  std::vector<ValueRef> in{q, k, v};
+  if (mask) in.push_back(*mask);
+  return add_layer(a, in, name)[0];
+}
+
 ValueRef ComputationGraph::layer_norm(ValueRef x, const std::vector<int64_t>& axes, bool affine, double eps,
                                       const std::string& name) {
   OpAttrs a(OpType::LAYERNORM);

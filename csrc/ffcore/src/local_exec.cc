@@ -1025,6 +1025,9 @@ LocalTrainingBacking::LocalTrainingBacking(const ComputationGraph& cg, LocalOpti
       init_weight(n, val_[{n, 0}], node.outputs[0].initializer, seed_);
       continue;
     }
+    if (t == OpType::SDPA)
+      throw FFError("local execution: scaled-dot-product attention (SDPA node " + node.label.name +
+                    ") is not supported");
     if (!reg.count(t)) throw FFError("local execution: no CPU implementation for " + to_string(t));
     if (t == OpType::MULTIHEAD_ATTENTION && cg_.layer_data_inputs(n).size() != 3)
       throw FFError("local execution: attention key lengths (the fourth input of " + node.label.name +

@@ -172,6 +172,12 @@ std::vector<MemoryPlan> plan_memory(const ParallelComputationGraph& pcg, const s
           const double out = static_cast<double>(o.num_elements());
           if (out > 0) own_extra[n] = extra / out;
         }
+      } else if (t == OpType::SDPA) {
+        // q, k, v, o and the mask are graph values (kept by the default
+        // rules below); on top of them only the fp32 LSE [B, H, Sq], two
+        // output-sized words per D outputs.  No Sq x Sk buffer.
+        const auto o = node_output_piece(pcg, n);
+        if (!o.dims.empty() && o.dims.back() > 0) own_extra[n] = 2.0 / static_cast<double>(o.dims.back());
       }
     }
   }

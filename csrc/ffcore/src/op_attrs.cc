@@ -732,6 +732,76 @@ OpSpec mha_spec() {
   return s;
 }
 
+// Scaled-dot-product attention without projections: q [B, H, Sq, D],
+// k / v [B, H, Sk, D] and an optional additive float mask broadcastable to
+// [B, H, Sq, Sk] (attribute mask = true: the fourth input) -> [B, H, Sq, D].
+// No weights; batch (dim 0) and heads (dim 1) shard freely, Sq / Sk / D do not.
+bool sdpa_has_mask(const OpAttrs& a) { return a.has("mask") && a.b("mask"); }
+
+OpSpec sdpa_spec() {
+  OpSpec s;
+  s.num_inputs = 3;
+  s.arity = [](const OpAttrs& a) { return sdpa_has_mask(a) ? 4 : 3; };
+  s.defaults = {{"causal", false}, {"dropout", 0.0}, {"scale", 0.0}, {"mask", false}};  // scale 0: 1 / sqrt(D)
+  s.weights = no_weights;
+  s.out = [](const OpAttrs& a, const Shapes& in) {
+    require(in.size() >= 3, a, "needs q, k, v");
+    for (int i = 0; i < 3; ++i) require(nd(in[i]) == 4, a, "q/k/v must be rank 4 [batch, heads, seq, head_dim]");
+    auto const &q = in[0], &k = in[1], &v = in[2];
+    require(q.dims[0] == k.dims[0] && q.dims[0] == v.dims[0], a, "batch mismatch");
+    require(q.dims[1] == k.dims[1] && q.dims[1] == v.dims[1], a,
+            "head count mismatch (grouped-query K / V heads are not supported)");
+    require(q.dims[3] == k.dims[3], a, "q/k head dim mismatch");
+    require(v.dims[3] == q.dims[3], a, "v's last dim must equal the head dim of q / k");
+    require(k.dims[2] == v.dims[2], a, "key/value sequence length mismatch");
+    require(a.f("dropout") >= 0.0 && a.f("dropout") < 1.0, a, "dropout must lie in [0, 1)");
+    require(sdpa_has_mask(a) == (in.size() > 3), a, "the mask attribute and the fourth input go together");
+    if (sdpa_has_mask(a)) {
+      auto const& m = in[3];
+      require(!a.b("causal"), a, "causal cannot be combined with a mask");
+      require(!is_integer_dtype(m.dtype) && m.dtype != DataType::BOOL, a,
+              "the mask must have a float dtype (convert a bool mask to additive 0 / -inf)");
+      require(nd(m) == 4, a, "the mask must be rank 4, broadcastable to [batch, heads, Sq, Sk]");
+      const int64_t full[4] = {q.dims[0], q.dims[1], q.dims[2], k.dims[2]};
+      for (int d = 0; d < 4; ++d)
+        require(m.dims[d] == full[d] || m.dims[d] == 1, a, "every mask dim must be 1 or the full extent");
+    }
+    if (a.b("causal")) require(q.dims[2] == k.dims[2], a, "causal needs Sq == Sk");
+    return Shapes{q};
+  };
+  s.wts = no_weight_shapes;
+  s.pout = [](const OpAttrs& a, const PShapes& in) {
+    require(in.size() >= 3, a, "needs q, k, v");
+    auto const& q = in[0];
+    for (int i = 0; i < 3; ++i) {
+      auto const& t = in[i];
+      require(t.num_dims() == 4, a, "q/k/v must be rank 4");
+      require(t.sum_degree == 1, a, "attention inputs cannot be partial sums");
+      require(t.dim(2).degree == 1 && t.dim(3).degree == 1, a,
+              "the sequence and head-dim dims must be unpartitioned (sequence parallelism is not offered)");
+      require(t.dim(0).degree == q.dim(0).degree && t.dim(1).degree == q.dim(1).degree, a,
+              "q/k/v batch / head degrees differ");
+      require(t.discard_copy_degree == q.discard_copy_degree, a, "q/k/v replica degrees differ");
+    }
+    Shapes red{in[0].reduced_shape(), in[1].reduced_shape(), in[2].reduced_shape()};
+    if (in.size() > 3) {
+      auto const& m = in[3];
+      require(m.num_dims() == 4, a, "the mask must be rank 4");
+      require(m.sum_degree == 1, a, "the mask cannot be a partial sum");
+      red.push_back(m.reduced_shape());
+      // a broadcast (size 1) dim stays whole, a full dim follows q
+      for (int d = 0; d < 2; ++d)
+        require(m.dim(d).degree == (red[3].dims[d] == 1 ? 1 : q.dim(d).degree), a,
+                "mask batch / head degree: 1 on a broadcast dim, q's degree on a full dim");
+      require(m.dim(2).degree == 1 && m.dim(3).degree == 1, a, "the mask's Sq / Sk dims must be unpartitioned");
+    }
+    auto o = registry()[static_cast<int>(OpType::SDPA)].out(a, red)[0];
+    return PShapes{lift_to_parallel_with_degrees(o, 1, q.discard_copy_degree, {q.dim(0).degree, q.dim(1).degree, 1, 1})};
+  };
+  s.pwts = no_pweight_shapes;
+  return s;
+}
+
 OpSpec batch_matmul_spec() {
   OpSpec s;
   s.num_inputs = 2;
@@ -1410,6 +1480,7 @@ std::unordered_map<int, OpSpec> build_registry() {
   put(OpType::SOFTMAX, softmax_spec());
   put(OpType::EMBEDDING, embedding_spec());
   put(OpType::MULTIHEAD_ATTENTION, mha_spec());
+  put(OpType::SDPA, sdpa_spec());
   put(OpType::BATCHMATMUL, batch_matmul_spec());
   put(OpType::MATMUL, batch_matmul_spec());
   put(OpType::CONCAT, concat_spec());
@@ -1562,6 +1633,17 @@ OpWork estimate_op_work(const OpAttrs& a, const std::vector<TensorShape>& in,
       // projections: every token through its per-head parameter block
       r.flops = 2 * b * sq * p * h + 4 * b * h * sq * sk * kd;
       if (a.b("causal")) r.flops -= 2 * b * h * sq * sk * kd;
+      r.matmul_like = true;
+      r.mfma_efficiency_hint = 0.8;
+      break;
+    }
+    case OpType::SDPA: {
+      // priced as MULTIHEAD_ATTENTION prices its attention part
+      double b = static_cast<double>(in[0].dims[0]), h = static_cast<double>(in[0].dims[1]);
+      double sq = static_cast<double>(in[0].dims[2]), sk = static_cast<double>(in[1].dims[2]);
+      double d = static_cast<double>(in[0].dims[3]);
+      r.flops = 4 * b * h * sq * sk * d;
+      if (a.b("causal")) r.flops -= 2 * b * h * sq * sk * d;
       r.matmul_like = true;
       r.mfma_efficiency_hint = 0.8;
       break;

@@ -73,6 +73,7 @@ bool is_mp_capable(const OpAttrs& op, MPKind k) {
       if (k == MPKind::ROW) return activation_from_string(op.s("activation")) == Activation::NONE;
       return false;
     case OpType::MULTIHEAD_ATTENTION: return k == MPKind::HEADS;
+    case OpType::SDPA: return k == MPKind::HEADS;  // a shard of the heads dim (dim 1): the op has no weights
     case OpType::EXPERTS: return k == MPKind::EXPERTS;
     case OpType::EMBEDDING: return k == MPKind::COLUMN && op.s("aggr") == "none";
     // conv channel parallelism (op-attrs conv_2d.cc:85-142): COLUMN = output
@@ -158,6 +159,15 @@ std::optional<std::vector<ParallelTensorShape>> required_input_shapes(const Comp
         break;
       }
       case MPKind::HEADS: {
+        if (op.type == OpType::SDPA) {
+          // q / k / v [batch, heads, seq, head_dim] shard on the heads dim; a
+          // mask follows where its heads dim is full and stays whole where it
+          // is 1 (its batch dim got q's degree above, the same way)
+          if (ref.num_dims() != 4 || ref.dims[1] % cfg.model) return std::nullopt;
+          for (auto& p : ps)
+            if (p.num_dims() == 4 && p.dim(1).size == ref.dims[1]) p.shard_dims[1].degree = cfg.model;
+          break;
+        }
         if (op.i("num_heads") % cfg.model) return std::nullopt;
         for (auto& p : ps) p.discard_copy_degree = cfg.model;
         break;

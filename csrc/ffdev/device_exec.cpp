@@ -749,6 +749,7 @@ std::string unsupported(const ComputationGraph& cg, int n) {
       if (ax[i] != nd - static_cast<int>(ax.size()) + static_cast<int>(i)) return "layer norm over non-trailing axes";
     return "";
   }
+  if (t == OpType::SDPA) return "scaled-dot-product attention (SDPA node " + node.label.name + ")";
   if (t == OpType::MULTIHEAD_ATTENTION) {
     const auto ins = cg.layer_data_inputs(n);
     if (ins.size() == 4) return "attention key lengths (the fourth input of " + node.label.name + ")";

@@ -31,8 +31,8 @@
 //    workgroup per (batch, head), all three gradients from one S / dS.
 //
 // Kernels: attn_fwd_kernel, attn_bwd_dq_kernel and attn_bwd_dkdv_kernel, each
-// for D in {64, 128} x CAUSAL x DROP x VARLEN (and, with VARLEN, PACKED), and
-// attn_bwd_onepass_kernel; attention_fwd / attention_bwd pick one through
+// for D in {64, 128} x CAUSAL x DROP x VARLEN (and, with VARLEN, PACKED) plus
+// D x DROP with BIAS, and attn_bwd_onepass_kernel; attention_fwd / attention_bwd pick one through
 // with_head and with_features.  Packed calls also launch
 // attn_segment_offsets_kernel (before) and attn_pack_tail_kernel (after).
 // Two environment switches: FFK_ATTN_PRIO (wave priority around the MFMA
@@ -119,6 +119,45 @@
 //    dV and lse = -inf (the GEMMs around attention reduce over all T rows).
 // kv_lens / q_lens, dbias in either form, Sq != Sk and the one-pass backward
 // are not part of the packed mode (std::invalid_argument; always the pair).
+//
+// Additive score bias (BIAS instantiations of the forward, dQ and dK/dV
+// kernels, D in {64, 128} with and without DROP, and only with CAUSAL =
+// VARLEN = PACKED = false; AttnTensors::bias).  fp32, element strides sb / sh
+// / sq for batch / head / query (0 = broadcast over that axis), the key axis
+// contiguous.  The score of (b, h, q, k) is scale * q.k + bias[b * sb + h * sh
+// + q * sq + k] before the softmax, i.e. in the log2 domain t = s * scale_log2
+// + bias * log2(e); -inf masks the pair.
+//  * forward: the bias enters as the initial value of the S^T accumulator
+//    (S' = K Q^T + bias / scale), so the running max, the lazy-rescale test
+//    and exp2 see t = S' * scale_log2 through the code of the unbiased kernel
+//    (the max of the raw q.k alone would be wrong).  A row with every key at
+//    -inf keeps m = -inf, l = 0: o = 0 and lse = -inf (torch gives NaN); the
+//    m == -inf guards keep NaN out on the way.
+//  * backward: P = exp2(t - lse).  A row whose lse is -inf has t = -inf
+//    everywhere; the dQ kernel takes its lse as +inf and the dK/dV kernel
+//    parks S' = -inf for it, so P = 0 (never exp2(-inf + inf)): dQ = 0, and
+//    the row adds nothing to dK / dV.  dS = P (keep rs dP - delta) and dQ =
+//    scale * dS K are unchanged.  No gradient is produced for the bias.
+//  * loads: in the forward and dQ kernels a lane owns one query and its
+//    registers hold four consecutive keys per group: one 16-byte load per
+//    group (bias_group).  In the dK/dV kernel a lane owns a key and its
+//    registers run over queries: 32 lanes read 128 consecutive bytes of a
+//    bias row.  The host requires a 16-byte aligned base, Sk % 4 == 0 and
+//    sb / sh / sq that are 0 or multiples of 4 (std::invalid_argument), so a
+//    group never straddles Sk; keys >= Sk and queries >= Sq are never read.
+//  * a tile's bias loads are issued ahead of its MFMAs and on the far side of
+//    the K / V (Q / dO) prefetch in issue order: vmcnt retires in order, so
+//    the wait for the bias leaves the prefetch in flight.
+//  * occupancy: the forward at D = 128 and the dK/dV kernel at D = 64 run one
+//    wave per SIMD with a bias (the unbiased forms run two): at two, the
+//    tile's 32 bias registers spilled into the tile loop.  No BIAS kernel has
+//    scratch (profiles/r7/attn_bias_isa.txt).
+//  * masked keys are still READ, unlike keys past kv_lens: K / V content
+//    under a mask must be finite (0 * NaN).  The dropout hash index is
+//    unchanged, (b * H + h, q * Sk + k).
+// Bias excludes causal, kv_lens, q_lens, seg_offsets and the fused dbias
+// (std::invalid_argument), and its backward is always the dQ + dK/dV pair.
+// A call without a bias runs the BIAS = false kernels, the code they were.
 #include <cstdlib>
 #include <type_traits>
 
@@ -160,7 +199,20 @@ struct AttnParams {
   // packed sequences (PACKED kernels only; B = packs, Sq = Sk = max_seqlen)
   const int32_t* seg_off;   // [B, M, 2]: clamped (start, len) of segment (n, m), from attn_segment_offsets_kernel
   int M, T;                 // segment slots per pack; physical tokens per pack
+  // additive score bias (BIAS kernels only): fp32, the key axis contiguous
+  const float* bias;
+  int64_t bias_sb, bias_sh, bias_sq;  // element strides of batch / head / query, 0 = broadcast
 };
+
+constexpr float kLog2e = 1.4426950408889634f;
+
+// Score bias (BIAS kernels): the four consecutive keys kg .. kg + 3 of one
+// query's bias row as one 16-byte load.  The host guarantees Sk % 4 == 0 and
+// 16-byte aligned rows, so a group lies wholly below Sk or wholly past it;
+// groups past Sk and rows past Sq (`ok` false) are never read.
+__device__ __forceinline__ f32x4 bias_group(const float* row, int kg, int Sk, bool ok) {
+  return (ok && kg < Sk) ? *reinterpret_cast<const f32x4*>(row + kg) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
 
 // Row of register r of a 32 x 32 MFMA accumulator, before the lane half's
 // + 4 h: registers 4g .. 4g+3 hold rows 8g .. 8g+3.
@@ -388,8 +440,11 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 // DROP: the dropped probabilities are zeroed after the row sum is taken, so
 // m, l and the LSE are those of the undropped softmax; the keep scale is
 // folded into the epilogue's 1 / l.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED>
-__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
+// BIAS at D = 128: one wave per SIMD.  At two (256 registers, of which the
+// unbiased form takes 246) the tile's 32 bias values spilled and were
+// reloaded inside the tile loop (68 - 188 bytes of scratch).
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS>
+__global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kernel(AttnParams P) {
   constexpr int KS = D / 16;        // k-steps over the head dim
   constexpr int DT = D / 32;        // 32-wide output tiles over the head dim
   constexpr int KV = 64;            // keys per tile
@@ -449,6 +504,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 
   int n_tiles = (Skl + KV - 1) / KV;
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
+  // bias: this query's row, at the lane half's first key
+  [[maybe_unused]] const float* brow = nullptr;
+  if constexpr (BIAS) brow = P.bias + b * P.bias_sb + hh * P.bias_sh + static_cast<int64_t>(q) * P.bias_sq + 4 * h;
 
   TileLoader<D, KV> kl, vl;
   kl.load(P.k, pn, hh, 0, Skl, ps);
@@ -475,6 +533,34 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
       n_tiles = 0;  // nothing left for the tile loop
     }
   }
+  // BIAS: the bias enters as the INITIAL VALUE of the S^T accumulator,
+  // S' = K Q^T + bias / scale, so that t = S' * scale_log2 = s * scale_log2 +
+  // bias * log2(e): the max, the lazy-rescale test and exp2 below then work
+  // on t through the code of the unbiased kernel (its "raw score" is S', the
+  // biased one), and a masked key (bias = -inf) has S' = -inf like a key past
+  // the sequence end.  Group kt * 4 + g of a tile holds the four keys of
+  // registers 4g .. 4g + 3 of s[kt].  A tile's groups are requested at the END
+  // of the tile before (here for tile 0), after that tile's P^T has been
+  // consumed (the allocator still gives them 32 registers of their own, which
+  // is what D = 128 pays one wave per SIMD for); they follow the K / V
+  // prefetch of the same tile in issue order and precede the next one, so the
+  // wait for them at the top of the tile (vmcnt retires in order) leaves the
+  // prefetch issued just before it in flight.  Kept raw until then: shaping
+  // them at the load would wait for the load there.
+  [[maybe_unused]] f32x16 bz[BIAS ? 2 : 1];
+  [[maybe_unused]] float bmul = 0.f;
+  auto load_bias = [&](int k0) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const f32x4 g = bias_group(brow, k0 + (i >> 2) * 32 + (i & 3) * 8, P.Sk - 4 * h, q_ok);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) bz[i >> 2][(i & 3) * 4 + e] = g[e];
+    }
+  };
+  if constexpr (BIAS) {
+    bmul = P.inv_scale_log2 * kLog2e;  // 1 / scale
+    load_bias(0);
+  }
   for (int t = 0; t < n_tiles; ++t) {
     const int k0 = t * KV;
     const unsigned char* Kt = smem + (t & 1) * 2 * TILE_BYTES;
@@ -492,6 +578,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         s[kt] = f32x16{};
+        if constexpr (BIAS) s[kt] = bz[kt] * bmul;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
           bf16x8 kf = lds_read16(Kt, lds_off<D>(kt * 32 + (lane & 31), 2 * ks + h));
@@ -569,6 +656,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
         }
       prio_lo(P);
     }
+    if constexpr (BIAS) {
+      // not to be scheduled up into the P^T V MFMAs, where s is still live
+      __builtin_amdgcn_sched_barrier(0);
+      if (has_next) load_bias(k0 + KV);
+    }
     if (has_next) {
       unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
       kl.store(nxt);
@@ -625,8 +717,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(AttnParams P) {
 // accumulates bq^T = K^T P^T from the K^T fragments of the dQ product (one
 // more MFMA product, DT more accumulators), and the epilogue adds
 // (dlt - delta) bq^T to dQ^T and writes delta for the dK / dV kernel.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED>
-__global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS>
+__global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, KV = 64;
   constexpr int TILE_BYTES = KV * D * 2;
   constexpr bool XDELTA = VARLEN && DROP;  // delta from the probabilities (comment above)
@@ -669,7 +761,12 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     qf[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.q.row(pn, ps + q, hh) + ks * 16 + 8 * h) : bf16x8{};
     df[ks] = q_live ? *reinterpret_cast<const bf16x8*>(P.dout.row(pn, ps + q, hh) + ks * 16 + 8 * h) : bf16x8{};
   }
-  const float lse = q_live ? P.lse[stat_index<PACKED>(P, bh, pn, hh, ps + q)] : 0.f;
+  float lse = q_live ? P.lse[stat_index<PACKED>(P, bh, pn, hh, ps + q)] : 0.f;
+  // bias: a row with every key masked has lse = -inf and t = -inf; taken as
+  // +inf here, t - lse is -inf and P = 0 (not exp2(-inf + inf))
+  if constexpr (BIAS) lse = (lse == -INFINITY) ? INFINITY : lse;
+  [[maybe_unused]] const float* brow = nullptr;
+  if constexpr (BIAS) brow = P.bias + b * P.bias_sb + hh * P.bias_sh + static_cast<int64_t>(q) * P.bias_sq + 4 * h;
   // lane (q, h) holds d = 16 ks + 8 h .. +8 of dO row q: a partial dot over
   // those, then the other half from lane ^ 32
   float part = 0.f;
@@ -751,6 +848,14 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
     const unsigned char* Kt = smem + (t & 1) * 2 * TILE_BYTES;
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
+    // bias of this tile, issued ahead of the next tile's K / V loads (see the
+    // forward): group kt * 4 + g holds the keys of registers 4g .. 4g + 3
+    [[maybe_unused]] f32x4 bz[BIAS ? 8 : 1];
+    if constexpr (BIAS) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i)
+        bz[i] = bias_group(brow, k0 + (i >> 2) * 32 + (i & 3) * 8, P.Sk - 4 * h, q_ok);
+    }
     if (has_next) {
       kl.load(P.k, pn, hh, k0 + KV, Skl, ps);
       vl.load(P.v, pn, hh, k0 + KV, Skl, ps);
@@ -770,7 +875,17 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
           dp = mfma32(lds_read16(Vt, off), df[ks], dp);
         }
         prio_lo(P);
-        if (need_mask) {
+        if constexpr (BIAS) {
+          // P = exp2(t - lse), t = s * scale_log2 + bias * log2(e); a masked
+          // key has t = -inf and P = 0
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const int key = k0 + kt * 32 + acc_row(r) + 4 * h;
+            float pv = fexp2(fmaf(s[r], P.scale_log2, bz[kt * 4 + (r >> 2)][r & 3] * kLog2e) - lse);
+            if (need_mask && (key >= Skl || !q_live)) pv = 0.f;
+            s[r] = pv * (kept(dp[r], k0, kt, r) - dlt);  // dS^T
+          }
+        } else if (need_mask) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + kt * 32 + acc_row(r) + 4 * h;
@@ -852,15 +967,16 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP ? 2 : 3) : 1)) void
 // hash index q * Sk + key steps by Sk per register; the dP accumulator starts
 // from zero and -delta is added after the keep scale (dS = P (keep rs dP -
 // delta)); dV takes keep . P and rs at the store.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED>
-__global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS>
+__global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32;
   // prefetched LDS fragments (below): GPT causal shape 0.341 -> 0.333 ms, BERT
   // within noise (profiles/ab_attn_bwd_pf_r3.txt).  At D = 128 (one wave /
   // SIMD) the prefetch registers spill; so they do with dropout at D = 64 (256
   // registers with no room for the hash: 40 - 72 bytes of scratch, reloaded in
   // the loop): those forms take the per-pair reads
-  constexpr bool PF = D == 64 && !DROP;
+  // (BIAS holds a tile's 32 bias values in their place)
+  constexpr bool PF = D == 64 && !DROP && !BIAS;
   constexpr int TILE_BYTES = QT * D * 2;
   constexpr int STAGE = 2 * TILE_BYTES + 2 * QT * 4;  // Q, dO, lse, delta
   __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
@@ -966,10 +1082,18 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
   auto park_scalars = [&](unsigned char* stage) {
     float* ls = reinterpret_cast<float*>(stage + 2 * TILE_BYTES);
     if (threadIdx.x < QT) {
-      ls[threadIdx.x] = nok ? -nls * P.inv_scale_log2 : -INFINITY;
+      // BIAS: a row with every key masked (lse = -inf) is parked like a row
+      // past Sq, S' = -inf and P = 0, not as +inf (exp2(inf - inf))
+      if constexpr (BIAS) ls[threadIdx.x] = (nok && nls > -INFINITY) ? -nls * P.inv_scale_log2 : -INFINITY;
+      else ls[threadIdx.x] = nok ? -nls * P.inv_scale_log2 : -INFINITY;
       ls[QT + threadIdx.x] = nok ? -nds : 0.f;
     }
   };
+  // bias: the lane's key column, at the lane half's first query row; register
+  // r of subtile qt is the row q0 + qt * 32 + acc_row(r) + 4 h, and the 32
+  // lanes of a half read 32 consecutive keys of it (128 bytes)
+  [[maybe_unused]] const float* bcol = nullptr;
+  if constexpr (BIAS) bcol = P.bias + b * P.bias_sb + hh * P.bias_sh + static_cast<int64_t>(4 * h) * P.bias_sq + key;
   // unconditional (rows past Sq load as zeros without touching memory): with
   // an `if (t0 < n_q_tiles)` around it the compiler kept a CFG path from the
   // K / V fragment loads above into the loop that skipped this block's
@@ -992,6 +1116,16 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
     const float* ls = reinterpret_cast<const float*>(stage + 2 * TILE_BYTES);
     const float* ds = ls + QT;
     const bool has_next = t + 1 < n_q_tiles;
+    // bias of this tile (bb[qt * 16 + r]), issued ahead of the next tile's
+    // Q / dO loads so that the wait for it leaves that prefetch in flight
+    [[maybe_unused]] float bb[BIAS ? 32 : 1];
+    if constexpr (BIAS) {
+#pragma unroll
+      for (int i = 0; i < 32; ++i) {
+        const int rq = q0 + (i >> 4) * 32 + acc_row(i & 15);
+        bb[i] = (k_ok && rq + 4 * h < P.Sq) ? bcol[static_cast<int64_t>(rq) * P.bias_sq] : 0.f;
+      }
+    }
     if (has_next) {
       ql.load(P.q, pn, hh, q0 + QT, Sql(), ps);
       dl.load(P.dout, pn, hh, q0 + QT, Sql(), ps);
@@ -1062,7 +1196,9 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
           for (int r = 0; r < 16; ++r) {
             const int rq = acc_row(r);
             const int qq = q0 + qt * 32 + rq + 4 * h;
-            float pv = fexp2(s[r] * P.scale_log2);
+            float e = s[r] * P.scale_log2;
+            if constexpr (BIAS) e = fmaf(s[r], P.scale_log2, bb[qt * 16 + r] * kLog2e);
+            float pv = fexp2(e);
             if (need_mask && (qq >= Sql() || (CAUSAL && key > qq) || !k_ok)) pv = 0.f;
             const bool drop = dropped(dq0 + static_cast<unsigned>(rq) * static_cast<unsigned>(P.Sk), dkey, P.drop_thr);
             dp[r] = pv * fmaf(drop ? 0.f : P.drop_rs, dp[r], ds[qt * 32 + rq + 4 * h]);
@@ -1072,7 +1208,9 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int qq = q0 + qt * 32 + acc_row(r) + 4 * h;
-            float pv = fexp2(s[r] * P.scale_log2);
+            float e = s[r] * P.scale_log2;
+            if constexpr (BIAS) e = fmaf(s[r], P.scale_log2, bb[qt * 16 + r] * kLog2e);
+            float pv = fexp2(e);
             if (qq >= Sql() || (CAUSAL && key > qq) || !k_ok) pv = 0.f;
             s[r] = pv;
             dp[r] = pv * dp[r];
@@ -1080,7 +1218,9 @@ __global__ __launch_bounds__(256, (D == 64 ? 2 : 1)) void attn_bwd_dkdv_kernel(A
         } else {
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const float pv = fexp2(s[r] * P.scale_log2);
+            float e = s[r] * P.scale_log2;
+            if constexpr (BIAS) e = fmaf(s[r], P.scale_log2, bb[qt * 16 + r] * kLog2e);
+            const float pv = fexp2(e);
             s[r] = pv;
             dp[r] = pv * dp[r];
           }
@@ -1532,6 +1672,22 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
     P.M = t.seg_M;
     P.T = t.seg_T;
   }
+  if (t.bias.p) {
+    // the BIAS kernels exist without any other axis but dropout
+    if (causal_grid) throw std::invalid_argument("attention: bias excludes causal (put the causal mask into the bias)");
+    if (t.kv_lens || t.q_lens) throw std::invalid_argument("attention: bias excludes kv_lens / q_lens");
+    if (t.seg_offsets) throw std::invalid_argument("attention: bias excludes packed sequences (seg_lens)");
+    if (t.dbq || t.dbk || t.dbv) throw std::invalid_argument("attention: bias excludes the fused dbias");
+    // one 16-byte load per four keys of a row
+    if (reinterpret_cast<uintptr_t>(t.bias.p) % 16) throw std::invalid_argument("attention: bias must be 16-byte aligned");
+    if (Sk % 4) throw std::invalid_argument("attention: bias needs Sk % 4 == 0");
+    if (t.bias.sb % 4 || t.bias.sh % 4 || t.bias.sq % 4 || t.bias.sb < 0 || t.bias.sh < 0 || t.bias.sq < 0)
+      throw std::invalid_argument("attention: bias strides must be 0 (broadcast) or positive multiples of 4");
+    P.bias = t.bias.p;
+    P.bias_sb = t.bias.sb;
+    P.bias_sh = t.bias.sh;
+    P.bias_sq = t.bias.sq;
+  }
   return P;
 }
 
@@ -1572,11 +1728,17 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
       if constexpr (VL) {
         if (packed) {
-          hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, true, true>), grid, block, 0, st, P);
+          hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, true, true, false>), grid, block, 0, st, P);
           return;
         }
       }
-      hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, VL, false>), grid, block, 0, st, P);
+      if constexpr (!CC && !VL) {
+        if (P.bias) {
+          hipLaunchKernelGGL((attn_fwd_kernel<DD, false, DR, false, false, true>), grid, block, 0, st, P);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, VL, false, false>), grid, block, 0, st, P);
     });
   });
   if (packed) launch_pack_tail(P, P.o_out, OutView{}, OutView{}, P.lse, B, D, st);
@@ -1604,7 +1766,7 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   const bool drop = P.drop_thr != 0, varlen = P.kv_lens || P.q_lens || packed;
   // a second key block needs the workspace: callers that pass none keep the
   // two-kernel path
-  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv || drop || varlen) && (Sk <= 256 || ws)) {
+  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv || drop || varlen || P.bias) && (Sk <= 256 || ws)) {
     hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(static_cast<unsigned>(B * H)), dim3(512), 0, st, P, ws);
     FFK_LAUNCH_CHECK("attention_bwd");
     return 1;
@@ -1619,13 +1781,20 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
       if constexpr (VL) {
         if (packed) {
-          hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, true, true>), gq, block, 0, st, P);
-          hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, true, true>), gk, block, 0, st, P);
+          hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, true, true, false>), gq, block, 0, st, P);
+          hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, true, true, false>), gk, block, 0, st, P);
           return;
         }
       }
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, VL, false>), gq, block, 0, st, P);
-      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, VL, false>), gk, block, 0, st, P);
+      if constexpr (!CC && !VL) {
+        if (P.bias) {
+          hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, false, DR, false, false, true>), gq, block, 0, st, P);
+          hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, false, DR, false, false, true>), gk, block, 0, st, P);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, VL, false, false>), gq, block, 0, st, P);
+      hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, DR, VL, false, false>), gk, block, 0, st, P);
     });
   });
   if (packed) launch_pack_tail(P, P.dq, P.dk, P.dv, nullptr, B, D, st);

@@ -130,6 +130,22 @@ struct AttnTensors {
   const int32_t* seg_offsets = nullptr;
   int seg_M = 0;
   int seg_T = 0;
+  // additive score bias / mask: fp32, broadcastable to [B, H, Sq, Sk] through
+  // the element strides sb / sh / sq (0 = broadcast over that axis), the key
+  // axis contiguous.  The score of (b, h, q, k) is scale * q.k + bias[b * sb +
+  // h * sh + q * sq + k] before the softmax; -inf masks the pair.  A row with
+  // every key masked gets o = 0, lse = -inf, dQ = 0.  Masked keys are still
+  // read (unlike with kv_lens): K / V under a mask must be finite.  No
+  // gradient is produced for the bias.  Needs a 16-byte aligned base,
+  // Sk % 4 == 0 and strides that are 0 or multiples of 4; excludes causal,
+  // kv_lens, q_lens, seg_offsets and the fused dbias (std::invalid_argument).
+  // Always the dQ + dK/dV kernel pair.  p = nullptr: no bias (the kernels of
+  // a call without one).
+  struct Bias {
+    const float* p = nullptr;
+    int64_t sb = 0, sh = 0, sq = 0;
+  };
+  Bias bias = {};
 };
 // seg_lens int32 [N, M] -> seg_off int32 [N, M, 2], both on the device: start =
 // sum of the pack's earlier clamped lengths, len clamped to [0, min(max_seqlen,

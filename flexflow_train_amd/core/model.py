@@ -590,6 +590,25 @@ class FFModel:
                          bias=bias, add_bias_kv=add_bias_kv, add_zero_attn=add_zero_attn, causal=causal,
                          seq_parallel_mode=seq_parallel_mode, **extra)
 
+    def scaled_dot_product_attention(self, q, k, v, mask=None, causal=False, dropout=0.0, scale=None, name=None):
+        """Attention without projections (the ``SDPA`` operator):
+        softmax(scale * q k^T + mask) v for ``q`` [batch, heads, Sq, D] and
+        ``k`` / ``v`` [batch, heads, Sk, D]; the result is [batch, heads, Sq, D].
+
+        ``mask``: optional float tensor broadcastable to [batch, heads, Sq, Sk]
+        (rank 4, every dim 1 or the full extent), added to the scores; -inf
+        masks a pair.  A row with every key masked gives zeros (torch gives
+        NaN).  The mask gets no gradient.  ``causal`` excludes a mask and needs
+        Sq == Sk.  ``dropout`` is applied to the probabilities in training.
+        ``scale``: None or 0 means 1 / sqrt(D).
+
+        bf16 on the GPU with D in {64, 128} and Sk % 4 == 0 runs on the flash
+        attention kernels (no Sq x Sk tensor exists); everything else takes a
+        torch fallback of the same definition."""
+        inputs = [q, k, v] + ([mask] if mask is not None else [])
+        return self._add("SDPA", inputs, name, causal=bool(causal), dropout=float(dropout),
+                         scale=float(scale or 0.0), mask=mask is not None)
+
     def experts(self, input, expert_ids, gate_weights, num_experts, hidden_size, out_dim=None,
                 activation=ActiMode.AC_MODE_RELU, use_bias=True, expert_parallel_mode="replicated", name=None):
         """Routed expert FFN block: ``input`` [B, D], ``expert_ids`` /

@@ -103,6 +103,7 @@ class OpType(Enum):
     MAX = 2053
     MIN = 2054
     MULTIHEAD_ATTENTION = 2060
+    SDPA = 2061
     GETITEM = 2070
     GETATTR = 2080
     EXPAND = 2081

@@ -38,6 +38,9 @@ class FFV:
     def __init__(self, t, shape=None):
         self.t = t
         self.shape = tuple(shape if shape is not None else t.dims)
+        # computed from a parameter (directly or through other operators): such
+        # a value needs a gradient path, which e.g. SDPA's mask input is not
+        self.from_param = False
 
 
 class Param:
@@ -111,7 +114,10 @@ class ATenImporter:
                 raise NotImplementedError(f"export node {node.op}")
             args = [self._val(env, a) for a in node.args]
             kwargs = {k: self._val(env, v) for k, v in node.kwargs.items()}
-            env[node.name] = self._call(node, args, kwargs)
+            env[node.name] = res = self._call(node, args, kwargs)
+            vals = list(args) + list(kwargs.values())
+            if self._has(vals, Param) or self._any_from_param(vals):
+                self._mark_from_param(res)
         ff._torch_weights = getattr(ff, "_torch_weights", {})
         ff._torch_weights.update(self.weights)
         return outs
@@ -131,6 +137,22 @@ class ATenImporter:
         if isinstance(x, (list, tuple)):
             return any(ATenImporter._has(v, kinds) for v in x)
         return False
+
+    @staticmethod
+    def _any_from_param(x) -> bool:
+        if isinstance(x, FFV):
+            return x.from_param
+        if isinstance(x, (list, tuple)):
+            return any(ATenImporter._any_from_param(v) for v in x)
+        return False
+
+    @staticmethod
+    def _mark_from_param(x):
+        if isinstance(x, FFV):
+            x.from_param = True
+        elif isinstance(x, (list, tuple)):
+            for v in x:
+                ATenImporter._mark_from_param(v)
 
     def _name(self, node) -> str:
         self._n += 1
@@ -393,12 +415,55 @@ class ATenImporter:
             out = ff.add(out, t, name=name if k == len(terms) - 2 else f"{name}_{k}")
         return FFV(out)
 
+    def _sdpa_fused(self, p, node, name):
+        """The SDPA node of an aten.scaled_dot_product_attention call, or None (see _sdpa)."""
+        q, k, v = (p[n] for n in ("query", "key", "value"))
+        if not all(isinstance(t, FFV) and len(t.shape) == 4 for t in (q, k, v)):
+            return None
+        if p.get("enable_gqa") or not (q.shape[1] == k.shape[1] == v.shape[1]):
+            return None
+        mask, causal = p.get("attn_mask"), bool(p.get("is_causal"))
+        if causal and (mask is not None or q.shape[2] != k.shape[2]):
+            return None
+        full = (q.shape[0], q.shape[1], q.shape[2], k.shape[2])
+        mt = None
+        if isinstance(mask, Param):
+            return None
+        if isinstance(mask, FFV):
+            if mask.from_param or len(mask.shape) != 4 or any(mask.shape[i] not in (1, full[i]) for i in range(4)):
+                return None
+            if mask.t.data_type not in (DataType.DT_FLOAT, DataType.DT_BFLOAT16, DataType.DT_HALF):
+                return None
+            mt = mask.t
+        elif isinstance(mask, torch.Tensor):
+            c = sdpa_const_mask(mask, full)
+            if c is None:
+                return None
+            mt = self.ff.create_constant_array(np.ascontiguousarray(c.numpy()), name=f"{node.name}_mask")
+        elif mask is not None:
+            return None
+        scale = p.get("scale")
+        return FFV(self.ff.scaled_dot_product_attention(q.t, k.t, v.t, mask=mt, causal=causal,
+                                                        dropout=float(p.get("dropout_p") or 0.0),
+                                                        scale=None if scale is None else float(scale), name=name))
+
     def _sdpa(self, args, kwargs, node, name):
-        """softmax(q k^T * scale + mask) v over (B, H, S, D) tensors."""
+        """softmax(q k^T * scale + mask) v over (B, H, S, D) tensors.
+
+        One SDPA node (flash attention, no [B, H, Sq, Sk] tensor) when q, k, v
+        are rank-4 FF tensors with equal head counts and the mask is absent, a
+        constant, or an FF tensor that no parameter feeds: bool masks become
+        additive 0 / -inf (not clamped: -inf is the kernels' "masked"),
+        is_causal and dropout_p become attributes.  A mask that depends on a
+        parameter (a learned position bias needs a gradient, which SDPA's mask
+        does not get), other ranks and enable_gqa keep the unfused chain below."""
         ff = self.ff
-        names = ["query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale"]
+        names = ["query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale", "enable_gqa"]
         p = dict(zip(names, args))
         p.update(kwargs)
+        fused = self._sdpa_fused(p, node, name)
+        if fused is not None:
+            return fused
         q, k, v = (self._ffv(p[n], node) for n in ("query", "key", "value"))
         d = q.shape[-1]
         scale = p.get("scale")
@@ -423,6 +488,24 @@ class ATenImporter:
             s = ff.add(s, self._ffv(mask, node).t, name=name + "_mask")
         pr = ff.softmax(s, nd - 1, name=name + "_softmax")
         return FFV(ff.batch_matmul(pr, v.t, name=name))
+
+
+def sdpa_const_mask(mask: torch.Tensor, full) -> Optional[torch.Tensor]:
+    """A constant attn_mask as SDPA's input: float32, rank 4, every dim 1 or
+    the full extent of [B, H, Sq, Sk]; bool (True = attend) becomes 0 / -inf.
+    None when it does not broadcast that way."""
+    mask = mask.detach()
+    if mask.dtype == torch.bool:
+        mask = torch.zeros(mask.shape).masked_fill(~mask.cpu(), float("-inf"))
+    elif not mask.dtype.is_floating_point:
+        return None
+    mask = mask.float()
+    if mask.dim() > 4:
+        return None
+    mask = mask.reshape((1,) * (4 - mask.dim()) + tuple(mask.shape))
+    if any(mask.shape[i] not in (1, full[i]) for i in range(4)):
+        return None
+    return mask
 
 
 class HFWrapper(torch.nn.Module):

@@ -47,6 +47,8 @@ class _Emitter:
         self.lines: List[str] = []
         self.out: Dict[str, object] = {}      # node name -> FF tensor (or tuple of tensors)
         self.weights: Dict[str, tuple] = {}    # FF layer name -> (weight name -> torch param)
+        self.const: Dict[str, torch.Tensor] = {}   # get_attr node name -> buffer (constant SDPA masks)
+        self.text_ir = False                       # the lines are the product (torch_to_string): no constants
 
     def line(self, name, ins, outs, op, *args):
         s = [name, INOUT_NODE_DELIMITER.join(ins) + (INOUT_NODE_DELIMITER if ins else ""),
@@ -87,6 +89,13 @@ class PyTorchModel:
             except Exception as e:   # data-dependent control flow etc.
                 self.trace_error = e
         self.modules = dict(self.model.named_modules())
+        if self.graph is not None:
+            # F.scaled_dot_product_attention maps to one SDPA node here; a call
+            # that does not fit it (a mask that a parameter feeds, grouped-query
+            # heads) has its unfused lowering in the torch.export path
+            why = next((w for w in (_sdpa_unfit(self, n) for n in self.graph.graph.nodes) if w), None)
+            if why:
+                self.graph, self.trace_error = None, NotImplementedError(why)
 
     def _export_to_ff(self, ffmodel, input_tensors: Sequence, verbose: bool):
         from .torch_export import ATenImporter, HFWrapper, _TORCH_DT
@@ -135,6 +144,7 @@ class PyTorchModel:
                                       "torch_to_ff (torch.export path)" +
                                       (f" (fx: {self.trace_error})" if self.trace_error else ""))
         em = _Emitter(None)
+        em.text_ir = True
         self._lower(em, None)
         return em.lines
 
@@ -169,7 +179,11 @@ class PyTorchModel:
             elif node.op in ("call_function", "call_method"):
                 _function(em, node)
             elif node.op == "get_attr":
-                raise NotImplementedError(f"get_attr {node.target} (module attributes are not supported)")
+                # a buffer is taken only as the constant mask of scaled_dot_product_attention
+                if not all(u.target is F.scaled_dot_product_attention and _sdpa_args(u).get("attn_mask") is node
+                           for u in node.users):
+                    raise NotImplementedError(f"get_attr {node.target} (module attributes are not supported)")
+                em.const[node.name] = _fetch_attr(self.model, node.target)
         return list(outputs)   # a list, as the reference's torch_to_ff / file_to_ff return
 
     def _module(self, em: _Emitter, node, mod: nn.Module):
@@ -270,6 +284,82 @@ _UNARY_FN = {F.relu: "RELU", torch.relu: "RELU", F.gelu: "GELU", torch.sigmoid: 
              "contiguous": "IDENTITY", "float": "IDENTITY"}
 
 
+_SDPA_ARGS = ["query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale", "enable_gqa"]
+
+
+def _sdpa_args(node) -> dict:
+    p = dict(zip(_SDPA_ARGS, node.args))
+    p.update(node.kwargs)
+    return p
+
+
+def _fetch_attr(model, target: str):
+    obj = model
+    for part in target.split("."):
+        obj = getattr(obj, part)
+    return obj
+
+
+def _param_fed(pm, node, memo) -> bool:
+    """Whether a parameter feeds the value of an fx node."""
+    if node not in memo:
+        memo[node] = False
+        if node.op == "call_module":
+            memo[node] = any(True for _ in pm.modules[node.target].parameters())
+        elif node.op == "get_attr":
+            memo[node] = isinstance(_fetch_attr(pm.model, node.target), nn.Parameter)
+        memo[node] = memo[node] or any(_param_fed(pm, i, memo) for i in node.all_input_nodes)
+    return memo[node]
+
+
+def _sdpa_unfit(pm, node) -> Optional[str]:
+    """Why a scaled_dot_product_attention call cannot become one SDPA node (None: it can, or is no such call)."""
+    if node.op != "call_function" or node.target is not F.scaled_dot_product_attention:
+        return None
+    p = _sdpa_args(node)
+    if p.get("enable_gqa"):
+        return "scaled_dot_product_attention with enable_gqa: imported through torch.export (unfused)"
+    mask = p.get("attn_mask")
+    if isinstance(mask, torch.fx.Node) and _param_fed(pm, mask, {}):
+        return ("scaled_dot_product_attention with a mask that depends on a parameter: imported through "
+                "torch.export (unfused, the bias gets a gradient)")
+    if mask is not None and p.get("is_causal"):
+        return "scaled_dot_product_attention with both attn_mask and is_causal"
+    return None
+
+
+def _sdpa(em: _Emitter, node):
+    """F.scaled_dot_product_attention -> one SDPA node (rules: torch_export._sdpa)."""
+    from .torch_export import sdpa_const_mask
+
+    ff, name = em.ff, node.name
+    p = _sdpa_args(node)
+    q, k, v, mask = (p.get(n) for n in _SDPA_ARGS[:4])
+    causal, dropout, scale = bool(p.get("is_causal")), float(p.get("dropout_p") or 0.0), p.get("scale")
+    const = isinstance(mask, torch.fx.Node) and mask.name in em.const
+    if const and em.text_ir:
+        raise NotImplementedError("the .ff text IR holds no tensor constants: scaled_dot_product_attention with a "
+                                  "constant mask is imported with torch_to_ff")
+    ins = [n.name for n in (q, k, v)] + ([mask.name] if isinstance(mask, torch.fx.Node) else [])
+    em.line(name, ins, [u.name for u in node.users], "SDPA", int(causal), dropout, 0.0 if scale is None else float(scale),
+            int(mask is not None))
+    if ff is None:
+        return
+    qt, kt, vt = (em.out.get(n.name) for n in (q, k, v))
+    mt = None
+    if const:
+        c = sdpa_const_mask(em.const[mask.name], (qt.dims[0], qt.dims[1], qt.dims[2], kt.dims[2]))
+        if c is None:
+            raise NotImplementedError(f"{name}: the constant mask is not broadcastable to [B, H, Sq, Sk]")
+        mt = ff.create_constant_array(c.numpy(), name=f"{name}_mask")
+    elif isinstance(mask, torch.fx.Node):
+        mt = em.out.get(mask.name)
+    elif mask is not None:
+        raise NotImplementedError(f"{name}: attn_mask must be a tensor")
+    em.out[name] = ff.scaled_dot_product_attention(qt, kt, vt, mask=mt, causal=causal, dropout=dropout, scale=scale,
+                                                   name=name)
+
+
 def _function(em: _Emitter, node):
     ff = em.ff
     name = node.name
@@ -283,7 +373,9 @@ def _function(em: _Emitter, node):
         if ff is not None and fn is not None:
             em.out[name] = fn()
 
-    if tgt in _BINARY:
+    if tgt is F.scaled_dot_product_attention:
+        _sdpa(em, node)
+    elif tgt in _BINARY:
         op = _BINARY[tgt]
         a, b = node.args[0], node.args[1]
         if isinstance(a, torch.fx.Node) and isinstance(b, torch.fx.Node):
@@ -435,6 +527,11 @@ def string_to_ff(lines: Sequence[str], ffmodel, input_tensors: Sequence):
         elif op == "MULTIHEAD_ATTENTION":
             q, k, v = (env[n] for n in ins[:3])
             env[name] = f.multihead_attention(q, k, v, int(a[0]), int(a[1]), name=name)
+        elif op == "SDPA":   # causal; dropout; scale (0: 1 / sqrt(D)); has mask (the fourth input)
+            q, k, v = (env[n] for n in ins[:3])
+            env[name] = f.scaled_dot_product_attention(q, k, v, mask=env[ins[3]] if int(a[3]) else None,
+                                                       causal=bool(int(a[0])), dropout=float(a[1]),
+                                                       scale=float(a[2]) or None, name=name)
         elif op == "SPLIT":
             import ast
 

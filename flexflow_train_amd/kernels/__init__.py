@@ -456,6 +456,60 @@ def _attn_q_lens(q_lens, q):
     return q_lens.data_ptr()
 
 
+def _attn_bias(bias, q, Sq, Sk, causal=False, kv_lens=None, q_lens=None, seg_lens=None, dbias=None):
+    """((ptr, sb, sh, sq), tensor) of an attention call's additive score bias,
+    or ((), None) without one.  The tensor is the fp32 storage the kernels
+    read (the argument itself, or its one-time upcast from bf16) and has to
+    outlive the launch.  Every rule of the BIAS kernels is checked here, by
+    name, before anything is launched."""
+    if bias is None:
+        return (), None
+    B, H = q.shape[0], q.shape[2]
+    if not isinstance(bias, torch.Tensor):
+        raise ValueError("attention: bias must be a tensor")
+    if bias.dtype == torch.bool:
+        raise ValueError("attention: a bool bias is not taken; convert it to an additive 0 / -inf mask")
+    if bias.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"attention: bias must be fp32 or bf16, got {bias.dtype}")
+    if bias.device != q.device:
+        raise ValueError("attention: bias must be on the device of q")
+    if causal:
+        raise ValueError("attention: bias cannot be combined with causal (put the causal mask into the bias)")
+    if kv_lens is not None or q_lens is not None:
+        raise ValueError("attention: bias cannot be combined with kv_lens / q_lens")
+    if seg_lens is not None:
+        raise ValueError("attention: bias cannot be combined with packed sequences (seg_lens)")
+    if dbias is not None:
+        raise ValueError("attention: bias cannot be combined with the fused dbias")
+    full = (B, H, Sq, Sk)
+    if bias.dim() != 4 or bias.shape[3] != Sk or any(bias.shape[i] not in (1, full[i]) for i in range(3)):
+        raise ValueError(f"attention: bias has shape {tuple(bias.shape)}, not broadcastable to [B, H, Sq, Sk] = "
+                         f"{list(full)} (rank 4, leading dims 1 or full, last dim Sk)")
+    if Sk % 4:
+        raise ValueError(f"attention: bias needs Sk % 4 == 0 (16-byte loads of four keys), got Sk = {Sk}")
+    if Sk > 1 and bias.stride(3) != 1:
+        raise ValueError("attention: the key axis (last dim) of bias must be contiguous (stride 1)")
+    if bias.dtype == torch.bfloat16:
+        # upcast once into a dense fp32 tensor of the bias's own (unexpanded) shape
+        shape = [bias.shape[i] if bias.stride(i) != 0 else 1 for i in range(3)] + [Sk]
+        src = bias[tuple(slice(0, n) for n in shape)].reshape(-1)
+        n = src.numel()
+        npad = (n + 7) // 8 * 8  # the cast kernel converts 8 values per thread
+        if npad != n:
+            src = torch.cat([src, src.new_zeros(npad - n)])
+        f32 = torch.empty(npad, device=bias.device, dtype=torch.float32)
+        cast_(src.contiguous(), f32)
+        bias = f32[:n].view(shape)
+    strides = [0 if bias.shape[i] == 1 else bias.stride(i) for i in range(3)]
+    if any(st % 4 or st < 0 for st in strides):
+        raise ValueError(f"attention: bias strides of batch / head / query must be 0 (broadcast) or multiples of 4, "
+                         f"got {strides}")
+    if bias.data_ptr() % 16:
+        raise ValueError("attention: bias must be 16-byte aligned")
+    STATS["attention_bias"] += 1
+    return (bias.data_ptr(), strides[0], strides[1], strides[2]), bias
+
+
 def attention_segment_offsets(seg_lens, T: int, max_seqlen: Optional[int] = None):
     """Clamped (start, len) of every segment of a packed batch: int32
     [N, M, 2] from ``seg_lens`` int32 [N, M], computed on the device (no host
@@ -515,7 +569,7 @@ def _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens, db
 
 
 def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None,
-                  q_lens=None, seg_lens=None, max_seqlen=None, seg_offsets=None):
+                  q_lens=None, seg_lens=None, max_seqlen=None, seg_offsets=None, bias=None):
     """Flash attention forward.  q,k,v: [B, S, H, D] bf16 views (any b/s/h
     strides, e.g. slices of a packed [B, S, 3, H, D] QKV buffer).
     Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain).
@@ -550,11 +604,23 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     lse = -inf and are never read.  ``max_seqlen`` (default T) bounds the
     segment length and sizes the grid.  ``seg_offsets``: the result of
     ``attention_segment_offsets`` for these arguments, if the caller already
-    has it.  Excludes ``kv_lens`` / ``q_lens`` and cross-attention."""
+    has it.  Excludes ``kv_lens`` / ``q_lens`` and cross-attention.
+
+    ``bias``: an additive score bias / mask, fp32 or bf16 (upcast once),
+    broadcastable to [B, H, Sq, Sk]: rank 4, each leading dim 1 or the full
+    extent (expanded zero-stride views are taken as broadcasts), the last dim
+    Sk with stride 1.  The score of (b, h, q, k) is scale * q.k + bias before
+    the softmax; -inf masks the pair.  A row with every key masked gives
+    o = 0 and lse = -inf (torch returns NaN for such a row).  Masked keys are
+    still read, unlike with ``kv_lens``: K / V under a mask must be finite.
+    Needs Sk % 4 == 0, a 16-byte aligned base and batch / head / query strides
+    that are 0 or multiples of 4; a bool bias is refused (convert it).
+    Excludes ``causal``, ``kv_lens`` / ``q_lens`` and ``seg_lens``."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
     if D not in (64, 128):
         raise ValueError("attention: head dim must be 64 or 128")
+    bview, bkeep = _attn_bias(bias, q, Sq, Sk, causal, kv_lens, q_lens, seg_lens)
     if seg_lens is not None:
         pk = _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens)
         if k.shape != (B, Sk, H, D) or v.shape != (B, Sk, H, D):
@@ -578,14 +644,15 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
     sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
     ext().attention_fwd(_view4(q), _view4(k), _view4(v), _view4(out), lse.data_ptr(), B, H, Sq, Sk, D, sc,
-                        bool(causal), _stream(), *drop, lens, **({"q_lens": qlens} if qlens else {}))
+                        bool(causal), _stream(), *drop, lens, **({"q_lens": qlens} if qlens else {}),
+                        **({"bias": bview} if bview else {}))
     STATS["attention_fwd"] += 1
     return out, lse
 
 
 def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False,
                   dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None, q_lens=None, seg_lens=None, max_seqlen=None,
-                  seg_offsets=None):
+                  seg_offsets=None, bias=None):
     """Flash-attention backward into dq / dk / dv; returns the path that ran
     (1: the one-pass kernel, 0: the dQ and dK/dV kernels).  ``dropout_p``,
     ``seed``, ``seed_dev``: those of the forward call that produced ``o``
@@ -602,9 +669,12 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     ``seg_lens``, ``max_seqlen``, ``seg_offsets``: the forward call's packed
     sequences (always path 0, no ``dbias``); every segment's rows of dq / dk /
     dv are written by its own workgroups and the rows past a pack's last
-    segment as zeros."""
+    segment as zeros.  ``bias``: the forward call's score bias (always path 0,
+    no ``dbias``); a row with every key masked gets dq = 0 and adds nothing to
+    dk / dv, and no gradient is produced for the bias itself."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
+    bview, bkeep = _attn_bias(bias, q, Sq, Sk, causal, kv_lens, q_lens, seg_lens, dbias)
     pk = None
     if seg_lens is not None:
         pk = _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens, dbias)
@@ -641,12 +711,13 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     drop = _attn_dropout_args(dropout_p, seed, seed_dev, q, Sq, Sk)
     lens = _attn_kv_lens(kv_lens, q)
     qlens = _attn_q_lens(q_lens, q)
-    n_ws = 0 if drop[0] else ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal), dbias is not None,
-                                                            bool(lens or qlens))
+    n_ws = 0 if drop[0] or bview else ext().attention_bwd_workspace(B, H, Sq, Sk, D, bool(causal),
+                                                                     dbias is not None, bool(lens or qlens))
     ws = torch.empty(n_ws, device=q.device, dtype=torch.float32) if n_ws else None
     path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
                                _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
-                               _stream(), *dbs, ld, _p(ws), *drop, lens, **({"q_lens": qlens} if qlens else {}))
+                               _stream(), *dbs, ld, _p(ws), *drop, lens, **({"q_lens": qlens} if qlens else {}),
+                               **({"bias": bview} if bview else {}))
     if path == 1:
         STATS["attention_bwd_onepass"] += 1
     if slab is not None:

@@ -1,4 +1,5 @@
-"""MULTIHEAD_ATTENTION operator (projections + flash attention + output proj).
+"""MULTIHEAD_ATTENTION operator (projections + flash attention + output proj)
+and SDPA, the same attention core without projections (end of this file).
 
 Parity: lib/local-execution/src/ops/attention.cc and lib/kernels/src/cuda/ops/
 attention_kernels.cu (cuDNN multi-head attention with fused projections;
@@ -154,9 +155,10 @@ def _torch_packed_attention(q, k, v, causal, scale, seg_lens, max_seqlen=None, d
     return o.transpose(1, 2).to(q.dtype)
 
 
-def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=None):
+def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=None, bias=None):
     # q,k,v: [B, S, H, D] -> [B, S, H, D]; drop = (keep mask [B, H, Sq, Sk], keep scale)
     # kv_lens, q_lens: [B] integer key / query lengths (module docstring)
+    # bias: additive float mask broadcastable to [B, H, Sq, Sk]; a row with every key at -inf gives zeros
     qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
     dead = qdead = None
     if q_lens is not None:
@@ -181,9 +183,17 @@ def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=Non
         Sq, Sk = s.shape[-2:]
         mask = torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1)
         s = s.masked_fill(mask, float("-inf"))
+    rowdead = None
+    if bias is not None:
+        s = s + bias.to(s.dtype)
+        # a row with every key masked: finite scores for the softmax, zeroed below
+        rowdead = torch.isneginf(s).all(-1, keepdim=True)
+        s = s.masked_fill(rowdead, 0.0)
     p = torch.softmax(s, -1)
     if dead is not None:
         p = p.masked_fill(dead[:, None, None, :], 0.0)
+    if rowdead is not None:
+        p = p.masked_fill(rowdead, 0.0)
     if drop is not None:
         p = p * drop[0].to(p.dtype) * drop[1]
     o = torch.matmul(p, vt.float())
@@ -591,3 +601,103 @@ class MultiHeadAttentionOp(OpImpl):
             else:
                 outs.append(None)
         return outs + no_lens_grad
+
+
+def _flash_bias_ok(mask, Sk) -> bool:
+    """The BIAS kernels' rules for a [*, *, *, Sk] float mask (kernels._attn_bias raises on them)."""
+    if mask.dtype not in (torch.float32, torch.bfloat16) or Sk % 4:
+        return False
+    if mask.dtype == torch.bfloat16:
+        return True   # upcast into a dense fp32 tensor by the kernel interface
+    if Sk > 1 and mask.stride(3) != 1:
+        return False
+    if any(mask.shape[i] != 1 and mask.stride(i) % 4 for i in range(3)):
+        return False
+    return mask.data_ptr() % 16 == 0
+
+
+@register("SDPA")
+class ScaledDotProductAttentionOp(OpImpl):
+    """softmax(scale * q k^T + mask) v without projections.
+
+    Inputs q [B, H, Sq, D], k / v [B, H, Sk, D] and an optional additive mask
+    broadcastable to [B, H, Sq, Sk] (float; -inf masks a pair; a bool mask, True
+    = attend, is converted); attributes ``causal``, ``dropout`` and ``scale``
+    (absent or 0: 1 / sqrt(D)).  Output [B, H, Sq, D].  A row with every key
+    masked gives zeros where torch gives NaN.  The mask gets no gradient: a
+    learned bias keeps the unfused operator chain in the importers.
+
+    bf16 on the GPU with D in {64, 128} runs on the flash kernels, which take
+    the [B, H, S, D] storage in place through [B, S, H, D] views (their
+    addressing is by stride); a mask goes to their BIAS instantiations when
+    Sk % 4 == 0 and its strides allow 16-byte loads.  Dropout draws its mask
+    from the operator's device step counter like MULTIHEAD_ATTENTION, so a
+    captured step gets a new mask per replay.  Everything else (CPU, fp32,
+    other head dims, Sk % 4 != 0, odd mask strides) runs _torch_attention,
+    the same definition in torch."""
+
+    def forward(self, ctx: OpContext, inputs, weights):
+        q, k, v = inputs[:3]
+        mask = inputs[3] if len(inputs) > 3 else None
+        if q.dim() != 4 or k.dim() != 4 or v.dim() != 4:
+            raise ValueError(f"{ctx.name}: q / k / v must be [batch, heads, seq, head_dim]")
+        B, H, Sq, D = q.shape
+        Sk = k.shape[2]
+        causal = bool(ctx.a("causal", False))
+        if causal and mask is not None:
+            raise ValueError(f"{ctx.name}: causal cannot be combined with a mask")
+        if causal and Sq != Sk:
+            raise ValueError(f"{ctx.name}: causal needs Sq == Sk")
+        scale = float(ctx.a("scale", 0.0) or 0.0) or 1.0 / math.sqrt(D)
+        if mask is not None:
+            if mask.dtype == torch.bool:
+                mask = torch.zeros(mask.shape, dtype=torch.float32, device=mask.device).masked_fill(~mask, float("-inf"))
+            elif not mask.dtype.is_floating_point:
+                raise ValueError(f"{ctx.name}: the mask must be a float or bool tensor, got {mask.dtype}")
+            elif mask.dtype not in (torch.float32, torch.bfloat16):
+                mask = mask.float()
+            full = (B, H, Sq, Sk)
+            if mask.dim() != 4 or any(mask.shape[i] not in (1, full[i]) for i in range(4)):
+                raise ValueError(f"{ctx.name}: mask shape {tuple(mask.shape)} is not broadcastable to {list(full)}")
+            if mask.shape[3] != Sk:
+                mask = mask.expand(*mask.shape[:3], Sk).contiguous()
+        p_drop = float(ctx.a("dropout", 0.0) or 0.0) if ctx.training else 0.0
+        drop = None
+        if p_drop > 0 and K.attention_dropout_threshold(p_drop):
+            drop = (p_drop, _drop_seed(ctx), _drop_step(ctx, q.device))
+        use_flash = (q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == q.dtype and v.dtype == q.dtype
+                     and D in (64, 128) and v.shape[3] == D and K.available()
+                     and (mask is None or _flash_bias_ok(mask, Sk)))
+        if use_flash:
+            q, k, v = (t if t.stride(3) == 1 and t.is_contiguous() else t.contiguous() for t in (q, k, v))
+            o = torch.empty(B, H, Sq, D, device=q.device, dtype=q.dtype)
+            kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+            _, lse = K.attention_fwd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal=causal,
+                                     scale=scale, out=o.transpose(1, 2), bias=mask, **kw)
+        else:
+            o = _torch_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, scale,
+                                 _fallback_mask(drop, B, H, Sq, Sk), bias=mask).transpose(1, 2).contiguous()
+            lse = None
+        return [o], (q, k, v, mask, o, lse, causal, scale, drop)
+
+    def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
+        q, k, v, mask, o, lse, causal, scale, drop = saved
+        B, H, Sq, D = q.shape
+        Sk = k.shape[2]
+        do = grad_outputs[0]
+        tail = [None] if mask is not None else []   # the mask gets no gradient
+        if lse is not None:
+            do = do.to(q.dtype).contiguous()
+            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+            kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+            t = lambda x: x.transpose(1, 2)
+            K.attention_bwd(t(q), t(k), t(v), t(o), lse, t(do), t(dq), t(dk), t(dv), causal=causal, scale=scale,
+                            bias=mask, **kw)
+        else:
+            qf, kf, vf = (x.detach().float().requires_grad_(True) for x in (q, k, v))
+            ref = _torch_attention(qf.transpose(1, 2), kf.transpose(1, 2), vf.transpose(1, 2), causal, scale,
+                                   _fallback_mask(drop, B, H, Sq, Sk), bias=mask)
+            ref.float().backward(do.float().transpose(1, 2))
+            dq, dk, dv = (x.grad.to(do.dtype) for x in (qf, kf, vf))
+        need = list(need_input_grad) + [False] * 3
+        return [dq if need[0] else None, dk if need[1] else None, dv if need[2] else None] + tail

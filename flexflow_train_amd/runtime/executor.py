@@ -131,6 +131,8 @@ class ParamPiece:
     numel: int = 0
     flat_id: int = 0
     final_step: int = -1          # forward index of first consumer
+    data_step: int = -1           # forward index of the first step that reads the weight as a DATA input
+    done_step: int = -1           # the earlier of the two: the backward step after which the gradient is complete
     n_consumers: int = 0
     grad_dtype: torch.dtype = torch.float32
     sparse: bool = False          # row-sparse SGD update (embedding tables)
@@ -683,7 +685,22 @@ class Executor:
                 p.n_consumers += 1
                 if p.final_step < 0:
                     p.final_step = idx
+            # a weight read as a DATA input (an imported ``x + self.param``, a
+            # learned attention bias): its gradient arrives as an input
+            # gradient of its consumers and is moved into the parameter's
+            # gradient at the first of them (_finish_data_params)
+            for v in dict.fromkeys(s.inputs):
+                p = self.param_of_value.get(v)
+                if p is not None:
+                    p.n_consumers += 1
+                    if p.data_step < 0:
+                        p.data_step = idx
         self.requires_grad = rg
+        self._data_param_final: Dict[int, List[ParamPiece]] = {}
+        for p in self.params:
+            p.done_step = min((i for i in (p.final_step, p.data_step) if i >= 0), default=-1)
+            if p.data_step >= 0:
+                self._data_param_final.setdefault(p.data_step, []).append(p)
 
     def _assign_params_to_buffers(self):
         dev = self.cfg.device
@@ -1208,6 +1225,7 @@ class Executor:
                                  self.cfg.device)
                 self.tracer.end(t0)
                 self._acc(grads, s.inputs[0], gi)
+                self._finish_data_params(i, s, grads, sync)
                 continue
             saved = self._saved.pop(i, None)
             if s.active:
@@ -1270,12 +1288,14 @@ class Executor:
                     for v, g, nd in zip(s.inputs, gins, need):
                         if g is not None and nd:
                             self._acc(grads, v, g)
+            self._finish_data_params(i, s, grads, sync)
             if sync:
                 for p in s.weights:
                     if p.final_step == i and p.trainable:
                         if p.regularizer is not None:
                             self._add_regularizer_grad(p)
-                        self._param_done(p)
+                        if p.done_step == i:
+                            self._param_done(p)
         self._saved = {}
         self._env = {}
         self._wg_join()
@@ -1334,6 +1354,20 @@ class Executor:
             grads[v] = grads[v] + g
         else:
             grads[v] = g
+
+    def _finish_data_params(self, i: int, s, grads, sync: bool):
+        """Step i of the backward is the last consumer to run of every weight
+        in _data_param_final[i] that operators read as a data input: the sum
+        of the input gradients they returned for it is its gradient."""
+        for p in self._data_param_final.get(i, ()):
+            g = grads.pop(p.terminal, None)
+            if not p.trainable:
+                continue
+            if g is not None and p.grad is not None:
+                p.grad.add_(g.reshape(p.grad.shape).to(p.grad.dtype))
+            # a step's own weights are finished by the caller
+            if sync and p.done_step == i and not (p.final_step == i and any(w is p for w in s.weights)):
+                self._param_done(p)
 
     def _param_done(self, p: ParamPiece):
         fb = self._param_bucket.get(id(p))

@@ -43,7 +43,8 @@ _TYPE_NAMES = {
     "embedding": "EMBEDDING", "linear": "LINEAR", "dense": "LINEAR", "concat": "CONCAT",
     "batch_matmul": "BATCHMATMUL", "batchmatmul": "BATCHMATMUL", "transpose": "TRANSPOSE", "conv2d": "CONV2D",
     "conv": "CONV2D", "pool2d": "POOL2D", "pool": "POOL2D", "softmax": "SOFTMAX", "attention": "MULTIHEAD_ATTENTION",
-    "multihead_attention": "MULTIHEAD_ATTENTION", "layer_norm": "LAYERNORM", "layernorm": "LAYERNORM",
+    "multihead_attention": "MULTIHEAD_ATTENTION", "sdpa": "SDPA", "scaled_dot_product_attention": "SDPA",
+    "layer_norm": "LAYERNORM", "layernorm": "LAYERNORM",
     "batch_norm": "BATCHNORM", "flat": "FLAT", "reshape": "RESHAPE", "dropout": "DROPOUT",
 }
 _LOSS_NAMES = ("mse_loss", "loss", "cross_entropy", "sparse_cross_entropy")

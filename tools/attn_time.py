@@ -9,6 +9,8 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
     python tools/attn_time.py --varlen [--dropout 0.1]                (per-sample key lengths against full length)
     python tools/attn_time.py --varlen --queries [--dropout 0.1]      (the same lengths as query lengths too)
     python tools/attn_time.py --packed [--dropout 0.1]                (packed sequences against the padded batch)
+    python tools/attn_time.py --bias key|full                         (additive mask / bias against no bias, kv_lens
+                                                                       and the unfused operator chain)
 
 --d128 appends two D = 128 shapes to whichever mode is run.
 """
@@ -250,7 +252,99 @@ def packed_ab(iters, rounds=5, seed=0, p=0.0):
         print(json.dumps(rec), flush=True)
 
 
+def bias_ab(kind, iters, rounds=5, seed=0):
+    """Interleaved same-process timing of the forward and the backward with an
+    additive score bias at the BERT-large and GPT-3-medium shapes, both
+    non-causal (the BIAS kernels have no causal form): `key` is a key-padding
+    mask [B, 1, 1, Sk] (0 / -inf, lengths uniform in [Sk / 8, Sk]), `full` a
+    finite fp32 bias [1, H, Sq, Sk].  Next to it, in the same rounds: the same
+    call without a bias, for `key` the call with kv_lens of the same lengths,
+    and the unfused operator chain (BATCHMATMUL, SCALAR_MULTIPLY, EW_ADD,
+    SOFTMAX, BATCHMATMUL on [B, H, S, D] tensors) forward and backward.
+    `act_bytes_*`: what each form keeps for its backward beside q / k / v / o
+    (the fp32 LSE against the bf16 probabilities [B, H, Sq, Sk])."""
+    import statistics
+
+    from flexflow_train_amd.ops import base as opbase
+
+    def op(t, **attrs):
+        return opbase.get_impl(t), opbase.OpContext(op_type=t, attrs=attrs, name=t.lower(), training=True,
+                                                    compute_dtype=torch.bfloat16, device=torch.device("cuda"))
+
+    for name in ("bert-large", "gpt3-medium"):
+        B, S, H, D, _ = SHAPES[name]
+        g = torch.Generator(device="cuda").manual_seed(0)
+        qkv = torch.randn(B, S, 3, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+        do = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        dqkv = torch.empty_like(qkv)
+        lens_cpu = torch.randint(S // 8, S + 1, (B,), generator=torch.Generator().manual_seed(seed), dtype=torch.int32)
+        if kind == "key":
+            bias = torch.zeros(B, 1, 1, S).masked_fill(torch.arange(S).view(1, 1, 1, S) >= lens_cpu.view(B, 1, 1, 1),
+                                                       float("-inf")).cuda()
+        else:
+            bias = 2 * torch.randn(1, H, S, S, device="cuda", generator=g)
+        variants = {"none": {}, "bias": dict(bias=bias)}
+        if kind == "key":
+            variants["kv_lens"] = dict(kv_lens=lens_cpu.cuda())
+        # the unfused chain on [B, H, S, D] copies
+        qh, kh, vh, doh = (t.transpose(1, 2).contiguous() for t in (q, k, v, do))
+        bm1, bm2, sc = op("BATCHMATMUL"), op("BATCHMATMUL"), op("SCALAR_MULTIPLY", scalar=1.0 / D ** 0.5)
+        add, sm, tr = op("EW_ADD"), op("SOFTMAX", dim=-1), op("TRANSPOSE", perm=[0, 1, 3, 2])
+        bias_c = bias.to(torch.bfloat16)
+
+        def chain_fwd():
+            saved = []
+
+            def run(o, ins, need):
+                outs, sv = o[0].forward(o[1], ins, [])
+                saved.append((o[0], o[1], sv, need))
+                return outs[0]
+
+            kt = run(tr, [kh], [True])
+            s = run(bm1, [qh, kt], [True, True])
+            s = run(sc, [s], [True])
+            s = run(add, [s, bias_c], [True, False])   # no gradient for the mask, as in SDPA
+            pr = run(sm, [s], [True])
+            return run(bm2, [pr, vh], [True, True]), saved
+
+        def chain_bwd(saved):
+            gr = doh
+            for impl, ctx, sv, need in reversed(saved):
+                grads = impl.backward(ctx, sv, [gr], [], need)
+                gr = grads[1] if impl is bm1[0] and ctx is bm1[1] else grads[0]   # dK^T goes on to the transpose
+
+        t = {}
+        for _ in range(rounds):
+            for tag, kw in variants.items():
+                o, lse = K.attention_fwd(q, k, v, **kw)
+                t.setdefault(("fwd", tag), []).append(_time(lambda: K.attention_fwd(q, k, v, out=o, **kw), iters))
+                t.setdefault(("bwd", tag), []).append(_time(
+                    lambda: K.attention_bwd(q, k, v, o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], **kw),
+                    iters))
+            _, saved = chain_fwd()
+            t.setdefault(("fwd", "unfused"), []).append(_time(lambda: chain_fwd(), max(3, iters // 5)))
+            t.setdefault(("bwd", "unfused"), []).append(_time(lambda: chain_bwd(saved), max(3, iters // 5)))
+            del saved
+        med = {key: statistics.median(x) for key, x in t.items()}
+        rec = {"shape": name + " non-causal", "bias": kind, "bias_shape": list(bias.shape),
+               "mean_len": round(float(lens_cpu.float().mean()), 1) if kind == "key" else None,
+               "act_bytes_flash": B * H * S * 4, "act_bytes_unfused": B * H * S * S * 2}
+        for which in ("fwd", "bwd"):
+            for tag in list(variants) + ["unfused"]:
+                rec[f"{which}_ms_{tag}"] = round(med[(which, tag)], 4)
+                rec[f"{which}_rounds_{tag}"] = [round(x, 4) for x in t[(which, tag)]]
+            rec[f"{which}_bias_over_none"] = round(med[(which, "bias")] / med[(which, "none")], 3)
+            rec[f"{which}_unfused_over_bias"] = round(med[(which, "unfused")] / med[(which, "bias")], 2)
+        print(json.dumps(rec), flush=True)
+
+
 def main():
+    if "--bias" in sys.argv:           # additive mask / bias against no bias, kv_lens and the unfused chain
+        kind = sys.argv[sys.argv.index("--bias") + 1]
+        if kind not in ("key", "full"):
+            raise SystemExit("--bias takes key or full")
+        return bias_ab(kind, 30)
     if "--packed" in sys.argv:         # packed sequences against the padded batch with key and query lengths
         return packed_ab(30, p=float(sys.argv[sys.argv.index("--dropout") + 1]) if "--dropout" in sys.argv else 0.0)
     if "--varlen" in sys.argv:         # per-sample key lengths against full length
