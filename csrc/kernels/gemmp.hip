@@ -532,6 +532,14 @@ void gemmp_bf16(const GemmPParams& p, hipStream_t st) {
       n = 256;
     return std::max(8, n);
   }();
+  // what no kernel of the family implements, refused for every variant (the
+  // launchers behind variants >= 1 would drop beta or write bf16 into an fp32 C)
+  const int epi = splits > 1 ? kEpiSplit : p.act_bwd ? kEpiDact : (p.bias || p.pre || p.act) ? kEpiBiasAct : kEpiPlain;
+  if (epi == kEpiBiasAct && p.beta != 0.f) throw std::invalid_argument("gemmp: bias / activation epilogue has no beta");
+  if (epi == kEpiDact && (p.beta != 0.f || p.out_f32 || p.bias || p.pre))
+    throw std::invalid_argument("gemmp: the activation-gradient epilogue writes bf16, no beta / bias / pre");
+  if (p.dbias && epi != kEpiDact) throw std::invalid_argument("gemmp: dbias needs the activation-gradient epilogue");
+  if (epi == kEpiBiasAct && p.out_f32) throw std::invalid_argument("gemmp: bias / activation epilogue writes bf16");
   if (p.variant == 11 && splits == 1 && gemmpp_supported(p)) {
     gemmpp_launch(p, st);
     return;
@@ -563,12 +571,6 @@ void gemmp_bf16(const GemmPParams& p, hipStream_t st) {
   }
   const int items = ((p.M + TM - 1) / TM) * ((p.N + TN - 1) / TN) * splits;
   dim3 grid(std::min(items, n_cu)), block(NTHREADS);  // persistent: one workgroup per CU
-  const int epi = splits > 1 ? kEpiSplit : p.act_bwd ? kEpiDact : (p.bias || p.pre || p.act) ? kEpiBiasAct : kEpiPlain;
-  if (epi == kEpiBiasAct && p.beta != 0.f) throw std::invalid_argument("gemmp: bias / activation epilogue has no beta");
-  if (epi == kEpiDact && (p.beta != 0.f || p.out_f32 || p.bias || p.pre))
-    throw std::invalid_argument("gemmp: the activation-gradient epilogue writes bf16, no beta / bias / pre");
-  if (p.dbias && epi != kEpiDact) throw std::invalid_argument("gemmp: dbias needs the activation-gradient epilogue");
-  if (epi == kEpiBiasAct && p.out_f32) throw std::invalid_argument("gemmp: bias / activation epilogue writes bf16");
   auto launch = [&](auto ta, auto tb) {
     constexpr bool TA = decltype(ta)::value, TB = decltype(tb)::value;
     switch (epi) {

@@ -351,7 +351,6 @@ __device__ __forceinline__ void epilogue(const GemmTArgs& g, f32x4t (&acc)[8][8]
     const bool mok = m_raw < g.M;
     const int m = mok ? m_raw : g.M - 1;
     const int64_t roff = static_cast<int64_t>(m) * g.ldc;
-    const float mf = mok ? 1.f : 0.f;
     if (EPI == kEpiDact && mb < 7) {
       const int64_t r1 = static_cast<int64_t>(row_of(mb + 1)) * g.ldc;
 #pragma unroll
@@ -389,8 +388,10 @@ __device__ __forceinline__ void epilogue(const GemmTArgs& g, f32x4t (&acc)[8][8]
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             v[h] = t_dact2<ACT>(v[h], unpack2(h ? xa[mb & 1][nb].y : xa[mb & 1][nb].x));
-            csum[nb][2 * h] += mf * v[h].x;  // masked rows add 0 (fp32 sum of the gradient)
-            csum[nb][2 * h + 1] += mf * v[h].y;
+            // masked rows add 0 (fp32 sum of the gradient): a select, since a
+            // masked row of a transposed, padded A may hold a neighbour's NaN
+            csum[nb][2 * h] += mok ? v[h].x : 0.f;
+            csum[nb][2 * h + 1] += mok ? v[h].y : 0.f;
           }
         }
         ob[nb] = uint2{pack2v(v[0]), pack2v(v[1])};
@@ -1449,14 +1450,18 @@ bool gemmt_supported(const GemmPParams& p) {
 }
 
 void gemmt_launch(const GemmPParams& p, int splits, int stage_mode, hipStream_t st) {
-  auto bytes = [](int rows, int ld) {
-    const uint64_t b = static_cast<uint64_t>(rows) * static_cast<uint64_t>(ld) * 2u;
+  // the buffer extent ends with the last row's last element: a padded view
+  // (ld > row length) may be the tail of its allocation, and the staging loads
+  // are not clamped to the operand's edge
+  auto bytes = [](int rows, int ld, int len) {
+    const uint64_t b = (static_cast<uint64_t>(rows - 1) * static_cast<uint64_t>(ld) + static_cast<uint64_t>(len)) * 2u;
     return static_cast<unsigned>(b > 0xFFFFFFFFull ? 0xFFFFFFFFull : b);
   };
   GemmTArgs g{static_cast<const bf16*>(p.A), static_cast<const bf16*>(p.B), p.C, p.workspace,
               static_cast<const bf16*>(p.bias), static_cast<bf16*>(p.pre), static_cast<const bf16*>(p.aux), p.dbias,
               p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.alpha, p.beta, p.act, p.act_bwd ? 1 : 0, p.out_f32, splits,
-              bytes(p.trans_a ? p.K : p.M, p.lda), bytes(p.trans_b ? p.N : p.K, p.ldb), p.dbg};
+              bytes(p.trans_a ? p.K : p.M, p.lda, p.trans_a ? p.M : p.K),
+              bytes(p.trans_b ? p.N : p.K, p.ldb, p.trans_b ? p.K : p.N), p.dbg};
   const int items = ((p.M + TM - 1) / TM) * ((p.N + TN - 1) / TN) * splits;
   dim3 grid(items), block(NTHREADS);
   const int epi = splits > 1                        ? kEpiSplit

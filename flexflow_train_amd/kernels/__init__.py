@@ -756,6 +756,8 @@ def gemm(a, b, trans_a=False, trans_b=False, bias=None, act="none", alpha=1.0, b
         _check(bias, "bias", torch.bfloat16, N)
     if pre is not None:
         _check(pre, "pre", torch.bfloat16, M * N)
+        if _ld2d(out) != N:   # the kernel indexes pre with ldc
+            raise ValueError("gemm: pre needs a dense output")
     splits = max(1, min(int(splits), (K + 63) // 64))
     if splits > 1 and (N % 4 or out.stride(0) % 4):
         splits = 1
@@ -838,6 +840,8 @@ def gemm256(a, b, trans_a=False, trans_b=False, bias=None, act="none", alpha=1.0
         _check(bias, "bias", torch.bfloat16, N)
     if pre is not None:
         _check(pre, "pre", torch.bfloat16, M * N)
+        if _ld2d(out) != N:   # the kernel indexes pre with ldc
+            raise ValueError("gemm256: pre needs a dense output")
     s = default_splits(M, N, K) if splits is None else int(splits)
     if bias is not None or pre is not None or act != "none":
         s = 1
@@ -884,6 +888,8 @@ def gemmp(a, b, trans_a=False, trans_b=False, bias=None, act="none", alpha=1.0, 
     for t, nm, n in ((bias, "bias", N), (pre, "pre", M * N), (aux, "aux", M * N)):
         if t is not None:
             _check(t, nm, torch.bfloat16, n)
+            if nm != "bias" and _ld2d(out) != N:   # the kernels index pre and aux with ldc
+                raise ValueError(f"gemmp: {nm} needs a dense output")
     if dbias is not None:
         _check(dbias, "dbias", torch.float32, N)
     if act_bwd and (aux is None or act == "none"):

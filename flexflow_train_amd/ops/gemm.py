@@ -114,7 +114,7 @@ def _blas(a, b, trans_a, trans_b, bias, act, out, beta, pre):
         else:
             out.copy_(r)
         return out
-    if act != "none":
+    if act != "none" or (pre is not None and not beta):
         # hipBLASLt GEMM (+ bias epilogue) writes the pre-activation directly,
         # the activation runs in the HIP element-wise kernel (16 B / lane).
         u = pre if pre is not None else torch.empty(A.shape[0], B.shape[1], device=A.device, dtype=A.dtype)
@@ -122,7 +122,9 @@ def _blas(a, b, trans_a, trans_b, bias, act, out, beta, pre):
             torch.addmm(bias, A, B, out=u)
         else:
             torch.mm(A, B, out=u)
-        if u.shape[-1] % 8 == 0:
+        if act == "none":   # pre-activation copy of a linear layer
+            y = u if out is not None else u.clone()
+        elif u.shape[-1] % 8 == 0:
             y, _ = K.bias_act_fwd(u, None, act)
         else:  # narrow heads (e.g. DLRM's 1-wide output) miss the 16-byte vector path
             y = _ACT[act](u)
@@ -253,10 +255,13 @@ def _lt(a, b, trans_a, trans_b, bias, act, out, beta, pre, algo=0):
     activation in the HIP element-wise kernel."""
     M = a.shape[1] if trans_a else a.shape[0]
     N = b.shape[0] if trans_b else b.shape[1]
-    if act != "none":
+    if act != "none" or (pre is not None and not beta):
         u = pre if pre is not None else torch.empty(M, N, device=a.device, dtype=torch.bfloat16)
         K.blaslt_matmul(a, b, trans_a, trans_b, u, 0.0, bias, algo)
-        y = K.bias_act_fwd(u, None, act)[0] if N % 8 == 0 else _ACT[act](u)
+        if act == "none":   # pre-activation copy of a linear layer
+            y = u if out is not None else u.clone()
+        else:
+            y = K.bias_act_fwd(u, None, act)[0] if N % 8 == 0 else _ACT[act](u)
         if out is not None:
             out.copy_(y)
             return out
@@ -485,6 +490,8 @@ def matmul(a: torch.Tensor, b: torch.Tensor, trans_a=False, trans_b=False, bias:
         return _f32(a, b, trans_a, trans_b, bias, act, out, beta, pre)
     hip_ok = _hip_ok(a, b, trans_a, trans_b) and (
         out is None or (out.stride(1) == 1 and out.stride(0) % 4 == 0 and out.data_ptr() % 8 == 0))
+    if pre is not None and out is not None and out.shape[0] > 1 and out.stride(0) != out.shape[1]:
+        hip_ok = False   # the kernels index pre with out's row stride: dense outputs only
     if not hip_ok or _MODE == "blas":
         return _blas(a, b, trans_a, trans_b, bias, act, out, beta, pre)
     if _MODE == "hip":
