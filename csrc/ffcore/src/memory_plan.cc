@@ -178,6 +178,18 @@ std::vector<MemoryPlan> plan_memory(const ParallelComputationGraph& pcg, const s
         // output-sized words per D outputs.  No Sq x Sk buffer.
         const auto o = node_output_piece(pcg, n);
         if (!o.dims.empty() && o.dims.back() > 0) own_extra[n] = 2.0 / static_cast<double>(o.dims.back());
+        // grouped-query K / V with a mask or dropout: the operator expands K
+        // and V to H heads and keeps both [B, H, Sk, D] copies for the backward
+        auto ins = pcg.layer_data_inputs(n);
+        const bool masked = op.has("mask") && op.b("mask");
+        const bool drops = op.has("dropout") && op.f("dropout") > 0.0;
+        if (ins.size() >= 3 && (masked || drops)) {
+          const auto q = pcg.shape(ins[0]).piece_shape(), k = pcg.shape(ins[1]).piece_shape();
+          if (q.dims.size() == 4 && k.dims.size() == 4 && k.dims[1] < q.dims[1] && o.num_elements() > 0) {
+            const double expanded = 2.0 * static_cast<double>(q.dims[0]) * q.dims[1] * k.dims[2] * k.dims[3];
+            own_extra[n] += expanded / static_cast<double>(o.num_elements());
+          }
+        }
       }
     }
   }

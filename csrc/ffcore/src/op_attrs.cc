@@ -733,9 +733,14 @@ OpSpec mha_spec() {
 }
 
 // Scaled-dot-product attention without projections: q [B, H, Sq, D],
-// k / v [B, H, Sk, D] and an optional additive float mask broadcastable to
+// k / v [B, Hkv, Sk, D] and an optional additive float mask broadcastable to
 // [B, H, Sq, Sk] (attribute mask = true: the fourth input) -> [B, H, Sq, D].
-// No weights; batch (dim 0) and heads (dim 1) shard freely, Sq / Sk / D do not.
+// Hkv divides H (grouped-query attention: query head h attends over K / V
+// head h / (H / Hkv); read from the shapes, no attribute); Hkv == H is plain
+// multi-head attention.  No weights; batch (dim 0) and heads (dim 1) shard
+// freely, Sq / Sk / D do not.  A head degree d must divide Hkv: contiguous
+// shards then keep h / G local (shard j holds query heads [j H / d, ...) and
+// K / V heads [j Hkv / d, ...)).
 bool sdpa_has_mask(const OpAttrs& a) { return a.has("mask") && a.b("mask"); }
 
 OpSpec sdpa_spec() {
@@ -749,8 +754,9 @@ OpSpec sdpa_spec() {
     for (int i = 0; i < 3; ++i) require(nd(in[i]) == 4, a, "q/k/v must be rank 4 [batch, heads, seq, head_dim]");
     auto const &q = in[0], &k = in[1], &v = in[2];
     require(q.dims[0] == k.dims[0] && q.dims[0] == v.dims[0], a, "batch mismatch");
-    require(q.dims[1] == k.dims[1] && q.dims[1] == v.dims[1], a,
-            "head count mismatch (grouped-query K / V heads are not supported)");
+    require(k.dims[1] == v.dims[1], a, "head count mismatch (k and v must have the same number of heads)");
+    require(k.dims[1] > 0 && q.dims[1] % k.dims[1] == 0, a,
+            "head count mismatch (grouped-query K / V heads must divide the query heads)");
     require(q.dims[3] == k.dims[3], a, "q/k head dim mismatch");
     require(v.dims[3] == q.dims[3], a, "v's last dim must equal the head dim of q / k");
     require(k.dims[2] == v.dims[2], a, "key/value sequence length mismatch");
@@ -781,6 +787,8 @@ OpSpec sdpa_spec() {
               "the sequence and head-dim dims must be unpartitioned (sequence parallelism is not offered)");
       require(t.dim(0).degree == q.dim(0).degree && t.dim(1).degree == q.dim(1).degree, a,
               "q/k/v batch / head degrees differ");
+      // grouped-query: whole groups per shard, so that h / G stays local
+      require(t.dim(1).size % t.dim(1).degree == 0, a, "the head degree must divide the K / V head count");
       require(t.discard_copy_degree == q.discard_copy_degree, a, "q/k/v replica degrees differ");
     }
     Shapes red{in[0].reduced_shape(), in[1].reduced_shape(), in[2].reduced_shape()};

@@ -160,12 +160,19 @@ std::optional<std::vector<ParallelTensorShape>> required_input_shapes(const Comp
       }
       case MPKind::HEADS: {
         if (op.type == OpType::SDPA) {
-          // q / k / v [batch, heads, seq, head_dim] shard on the heads dim; a
-          // mask follows where its heads dim is full and stays whole where it
-          // is 1 (its batch dim got q's degree above, the same way)
-          if (ref.num_dims() != 4 || ref.dims[1] % cfg.model) return std::nullopt;
-          for (auto& p : ps)
-            if (p.num_dims() == 4 && p.dim(1).size == ref.dims[1]) p.shard_dims[1].degree = cfg.model;
+          // q / k / v [batch, heads, seq, head_dim] shard on the heads dim, by
+          // position: k / v may have fewer heads than q (grouped-query), and
+          // the degree must divide their count so that every shard holds
+          // whole groups.  A mask (input 3) follows where its heads dim is
+          // full and stays whole where it is 1 (its batch dim got q's degree
+          // above, the same way)
+          if (ref.num_dims() != 4 || ref.dims[1] % cfg.model || ps.size() < 3) return std::nullopt;
+          for (size_t i = 0; i < 3; ++i) {
+            if (ps[i].num_dims() != 4 || ps[i].dim(1).size % cfg.model) return std::nullopt;
+            ps[i].shard_dims[1].degree = cfg.model;
+          }
+          if (ps.size() > 3 && ps[3].num_dims() == 4 && ps[3].dim(1).size == ref.dims[1])
+            ps[3].shard_dims[1].degree = cfg.model;
           break;
         }
         if (op.i("num_heads") % cfg.model) return std::nullopt;

@@ -32,8 +32,9 @@
 //
 // Kernels: attn_fwd_kernel, attn_bwd_dq_kernel and attn_bwd_dkdv_kernel, each
 // for D in {64, 128} x CAUSAL x DROP x VARLEN (and, with VARLEN, PACKED) plus
-// D x DROP with BIAS, and attn_bwd_onepass_kernel; attention_fwd / attention_bwd pick one through
-// with_head and with_features.  Packed calls also launch
+// D x DROP with BIAS and D x CAUSAL with GQA, and attn_bwd_onepass_kernel;
+// attention_fwd / attention_bwd pick one through with_head and
+// with_features.  Packed calls also launch
 // attn_segment_offsets_kernel (before) and attn_pack_tail_kernel (after).
 // Two environment switches: FFK_ATTN_PRIO (wave priority around the MFMA
 // clusters; default on at D = 128) and FFK_ATTN_BWD_ONEPASS (0: the kernel
@@ -158,6 +159,36 @@
 // Bias excludes causal, kv_lens, q_lens, seg_offsets and the fused dbias
 // (std::invalid_argument), and its backward is always the dQ + dK/dV pair.
 // A call without a bias runs the BIAS = false kernels, the code they were.
+//
+// Grouped-query attention (GQA instantiations of the forward, dQ and dK/dV
+// kernels, D in {64, 128} x CAUSAL, and only with DROP = VARLEN = PACKED =
+// BIAS = false; AttnTensors::kv_heads).  K, V, dK and dV have Hkv heads, Hkv
+// dividing H, G = H / Hkv; query head h attends over K / V head h / G (torch's
+// enable_gqa, repeat_interleave(G) over the heads), and dK[hk] / dV[hk] are
+// the sums of the per-query-head gradients over h in [hk * G, (hk + 1) * G).
+//  * forward and dQ: the grid stays over the B * H query heads.  The head of
+//    every K / V row address and tile load is hh / G (kv_head), uniform over
+//    the workgroup and so a scalar; Q, O, dO, dQ, LSE and delta stay on the
+//    query head.  A query head does the arithmetic of the H-head call on the
+//    same bits: o, lse and dq equal those of a call on K / V expanded to H
+//    heads bit for bit.
+//  * dK/dV: the grid is over the B * Hkv K / V heads.  A workgroup loads its
+//    K / V fragments once and runs the query-tile loop for each of the G
+//    query heads of its group as one flat sequence of (head, tile) steps, so
+//    the LDS double buffer and the prefetch run across head boundaries and
+//    every barrier stays workgroup-uniform; Q / dO tiles, LSE and delta are
+//    those of query head hk * G + g (rows (b * H + hk * G + g) * Sq + q);
+//    with CAUSAL each head starts again at the key block's first tile.  dK
+//    and dV accumulate in the fp32 registers over the whole group and are
+//    stored once, with one bf16 rounding (summing per-head bf16 gradients of
+//    an expanded call rounds G + 1 times).
+//  * occupancy: __launch_bounds__ are those of the forms without GQA; no GQA
+//    kernel has scratch (profiles/r7/attn_gqa_isa.txt).
+//  * the dK/dV grid has G times fewer workgroups than an H-head call's, B *
+//    Hkv * ceil(Sk / 128); splitting a group over workgroups is not done.
+// GQA excludes dropout, kv_lens, q_lens, seg_offsets, bias and the fused dbias
+// (std::invalid_argument), and its backward is always the dQ + dK/dV pair.  A
+// call with Hkv == H runs the GQA = false kernels, the code they were.
 #include <cstdlib>
 #include <type_traits>
 
@@ -202,6 +233,8 @@ struct AttnParams {
   // additive score bias (BIAS kernels only): fp32, the key axis contiguous
   const float* bias;
   int64_t bias_sb, bias_sh, bias_sq;  // element strides of batch / head / query, 0 = broadcast
+  // grouped-query attention (GQA kernels only): K / V have Hkv heads, G = H / Hkv
+  int Hkv, G;
 };
 
 constexpr float kLog2e = 1.4426950408889634f;
@@ -234,6 +267,14 @@ template <bool VARLEN>
 __device__ __forceinline__ int query_len(const AttnParams& P, int b) {
   if constexpr (VARLEN) return P.q_lens ? __builtin_amdgcn_readfirstlane(min(max(P.q_lens[b], 0), P.Sq)) : P.Sq;
   else return P.Sq;
+}
+
+// K / V head of query head hh.  GQA: hh / G, uniform over the workgroup (hh
+// derives from the block id), so a scalar.  Otherwise the query head itself.
+template <bool GQA>
+__device__ __forceinline__ int kv_head(const AttnParams& P, int hh) {
+  if constexpr (GQA) return hh / P.G;
+  else return hh;
 }
 
 // Packed sequences: the segment a workgroup serves.  `b` of the grid is the
@@ -443,7 +484,7 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 // BIAS at D = 128: one wave per SIMD.  At two (256 registers, of which the
 // unbiased form takes 246) the tile's 32 bias values spilled and were
 // reloaded inside the tile loop (68 - 188 bytes of scratch).
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false>
 __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kernel(AttnParams P) {
   constexpr int KS = D / 16;        // k-steps over the head dim
   constexpr int DT = D / 32;        // 32-wide output tiles over the head dim
@@ -458,6 +499,7 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
   int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;
   if (!CAUSAL) attn_head_block(bh, qb);
   const int b = bh / P.H, hh = bh % P.H;
+  const int hk = kv_head<GQA>(P, hh);  // the head of every K / V address; all else stays on hh
   // packed: b is a segment; its rows are ps .. ps + plen of pack pn
   [[maybe_unused]] int pn = b, ps = 0, plen = 0;
   if constexpr (PACKED) {
@@ -509,8 +551,8 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
   if constexpr (BIAS) brow = P.bias + b * P.bias_sb + hh * P.bias_sh + static_cast<int64_t>(q) * P.bias_sq + 4 * h;
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, pn, hh, 0, Skl, ps);
-  vl.load(P.v, pn, hh, 0, Skl, ps);
+  kl.load(P.k, pn, hk, 0, Skl, ps);
+  vl.load(P.v, pn, hk, 0, Skl, ps);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -522,8 +564,8 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
     if (__builtin_amdgcn_readfirstlane(qw) >= Sql) {
       for (int t = 0; t < n_tiles; ++t) {
         if (t + 1 < n_tiles) {
-          kl.load(P.k, pn, hh, (t + 1) * KV, Skl, ps);
-          vl.load(P.v, pn, hh, (t + 1) * KV, Skl, ps);
+          kl.load(P.k, pn, hk, (t + 1) * KV, Skl, ps);
+          vl.load(P.v, pn, hk, (t + 1) * KV, Skl, ps);
           unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
           kl.store(nxt);
           vl.store(nxt + TILE_BYTES);
@@ -567,8 +609,8 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
     if (has_next) {  // issue next tile's HBM loads before this tile's MFMAs
-      kl.load(P.k, pn, hh, k0 + KV, Skl, ps);
-      vl.load(P.v, pn, hh, k0 + KV, Skl, ps);
+      kl.load(P.k, pn, hk, k0 + KV, Skl, ps);
+      vl.load(P.v, pn, hk, k0 + KV, Skl, ps);
     }
     const bool wave_active = !CAUSAL || (k0 <= qw + 31);
     if (wave_active) {
@@ -717,7 +759,7 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
 // accumulates bq^T = K^T P^T from the K^T fragments of the dQ product (one
 // more MFMA product, DT more accumulators), and the epilogue adds
 // (dlt - delta) bq^T to dQ^T and writes delta for the dK / dV kernel.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false>
 __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, KV = 64;
   constexpr int TILE_BYTES = KV * D * 2;
@@ -727,6 +769,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
   int bh = blockIdx.x, qb = gridDim.y - 1 - blockIdx.y;   // causal: longest-first (fwd)
   if (!CAUSAL) attn_head_block(bh, qb);
   const int b = bh / P.H, hh = bh % P.H;
+  const int hk = kv_head<GQA>(P, hh);  // the head of every K / V address; all else stays on hh
   // packed: b is a segment; its rows are ps .. ps + plen of pack pn
   [[maybe_unused]] int pn = b, ps = 0, plen = 0;
   if constexpr (PACKED) {
@@ -811,8 +854,8 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, pn, hh, 0, Skl, ps);
-  vl.load(P.v, pn, hh, 0, Skl, ps);
+  kl.load(P.k, pn, hk, 0, Skl, ps);
+  vl.load(P.v, pn, hk, 0, Skl, ps);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -831,8 +874,8 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
     if (__builtin_amdgcn_readfirstlane(qw) >= Sql) {
       for (int t = 0; t < n_tiles; ++t) {
         if (t + 1 < n_tiles) {
-          kl.load(P.k, pn, hh, (t + 1) * KV, Skl, ps);
-          vl.load(P.v, pn, hh, (t + 1) * KV, Skl, ps);
+          kl.load(P.k, pn, hk, (t + 1) * KV, Skl, ps);
+          vl.load(P.v, pn, hk, (t + 1) * KV, Skl, ps);
           unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
           kl.store(nxt);
           vl.store(nxt + TILE_BYTES);
@@ -857,8 +900,8 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
         bz[i] = bias_group(brow, k0 + (i >> 2) * 32 + (i & 3) * 8, P.Sk - 4 * h, q_ok);
     }
     if (has_next) {
-      kl.load(P.k, pn, hh, k0 + KV, Skl, ps);
-      vl.load(P.v, pn, hh, k0 + KV, Skl, ps);
+      kl.load(P.k, pn, hk, k0 + KV, Skl, ps);
+      vl.load(P.v, pn, hk, k0 + KV, Skl, ps);
     }
     const bool wave_active = !CAUSAL || (k0 <= qw + 31);
     const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= (VARLEN ? Sql : P.Sq));
@@ -967,7 +1010,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
 // hash index q * Sk + key steps by Sk per register; the dP accumulator starts
 // from zero and -delta is added after the keep scale (dS = P (keep rs dP -
 // delta)); dV takes keep . P and rs at the store.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS>
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false>
 __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
   constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32;
   // prefetched LDS fragments (below): GPT causal shape 0.341 -> 0.333 ms, BERT
@@ -984,7 +1027,8 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
   // causal: heads fastest, key block 0 (the most query tiles) first — longest first
   int bh = blockIdx.x, kb = blockIdx.y;
   if (!CAUSAL) attn_head_block(bh, kb);
-  const int b = bh / P.H, hh = bh % P.H;
+  // GQA: the grid runs over the B * Hkv K / V heads and hh is the K / V head
+  const int b = bh / (GQA ? P.Hkv : P.H), hh = bh % (GQA ? P.Hkv : P.H);
   const int k_blk = kb * (4 * KW);
   // packed: b is a segment; its rows are ps .. ps + plen of pack pn.  Held as
   // constants (and fetch_scalars below keeps its index form per mode): as
@@ -1039,6 +1083,20 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
   // loop of a live block ends at the sample's last live query tile
   const int n_q_tiles = (VARLEN && k_blk >= Skl()) ? 0 : (Sql() + QT - 1) / QT;
   const int t0 = CAUSAL ? (k_blk / QT) : 0;
+  // GQA: this workgroup serves the G query heads hh * G .. of its K / V head,
+  // one after another, as ONE sequence of (head, query tile) steps: t runs
+  // over t0 .. t_end, G times the tiles of a head (each head starts again at
+  // t0, the key block's first causal tile), so the double buffer, the prefetch
+  // and the one barrier per step carry on across the head boundaries and dK /
+  // dV stay in the accumulators for the whole group.  hq / tq are the head
+  // and the head's tile of step t; both are uniform over the workgroup.
+  int t_end = n_q_tiles;
+  [[maybe_unused]] int hq = hh, tq = t0, hq_n = hh, tq_n = t0, f_sbh = 0;
+  if constexpr (GQA) {
+    t_end = t0 + P.G * max(n_q_tiles - t0, 0);
+    hq = hq_n = hh * P.G;
+    f_sbh = b * P.H + hq;
+  }
   // dropout: hash index of register r of a subtile = (first query + 4 h +
   // acc_row(r)) * Sk + key
   [[maybe_unused]] unsigned dkey = 0, dcol = 0;
@@ -1072,6 +1130,12 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
         nls = P.lse[stat_index<true>(P, bh, pn, hh, ps + qq)];
         nds = P.delta[stat_index<true>(P, bh, pn, hh, ps + qq)];
       }
+    } else if constexpr (GQA) {
+      // the rows of the query head being fetched: (b * H + hk * G + g) * Sq + q
+      if (nok) {
+        nls = P.lse[static_cast<int64_t>(f_sbh) * P.Sq + qq];
+        nds = P.delta[static_cast<int64_t>(f_sbh) * P.Sq + qq];
+      }
     } else {
       if (nok) {
         nls = P.lse[static_cast<int64_t>(bh) * P.Sq + qq];
@@ -1100,22 +1164,22 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
   // vmcnt(0), so the first MFMA of EVERY iteration waited on vmcnt — and
   // vmcnt retires in order, so that wait drained the next tile's prefetch
   // right after issuing it (one exposed global-load latency per tile)
-  ql.load(P.q, pn, hh, t0 * QT, Sql(), ps);
-  dl.load(P.dout, pn, hh, t0 * QT, Sql(), ps);
+  ql.load(P.q, pn, hq, t0 * QT, Sql(), ps);
+  dl.load(P.dout, pn, hq, t0 * QT, Sql(), ps);
   fetch_scalars(t0 * QT);
   ql.store(smem);
   dl.store(smem + TILE_BYTES);
   park_scalars(smem);
   __syncthreads();
 
-  for (int t = t0; t < n_q_tiles; ++t) {
-    const int q0 = t * QT;
+  for (int t = t0; t < t_end; ++t) {
+    const int q0 = (GQA ? tq : t) * QT;
     unsigned char* stage = smem + ((t - t0) & 1) * STAGE;
     const unsigned char* Qt = stage;
     const unsigned char* Dt = stage + TILE_BYTES;
     const float* ls = reinterpret_cast<const float*>(stage + 2 * TILE_BYTES);
     const float* ds = ls + QT;
-    const bool has_next = t + 1 < n_q_tiles;
+    const bool has_next = t + 1 < t_end;
     // bias of this tile (bb[qt * 16 + r]), issued ahead of the next tile's
     // Q / dO loads so that the wait for it leaves that prefetch in flight
     [[maybe_unused]] float bb[BIAS ? 32 : 1];
@@ -1126,7 +1190,19 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
         bb[i] = (k_ok && rq + 4 * h < P.Sq) ? bcol[static_cast<int64_t>(rq) * P.bias_sq] : 0.f;
       }
     }
-    if (has_next) {
+    if constexpr (GQA) {
+      // the next step: this head's next tile, or the first tile of the
+      // group's next head (has_next: there is one)
+      const bool wrap = tq + 1 == n_q_tiles;
+      tq_n = wrap ? t0 : tq + 1;
+      hq_n = wrap ? hq + 1 : hq;
+      if (has_next) {
+        f_sbh = b * P.H + hq_n;
+        ql.load(P.q, pn, hq_n, tq_n * QT, Sql(), ps);
+        dl.load(P.dout, pn, hq_n, tq_n * QT, Sql(), ps);
+        fetch_scalars(tq_n * QT);
+      }
+    } else if (has_next) {
       ql.load(P.q, pn, hh, q0 + QT, Sql(), ps);
       dl.load(P.dout, pn, hh, q0 + QT, Sql(), ps);
       fetch_scalars(q0 + QT);
@@ -1253,6 +1329,7 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
       park_scalars(nxt);
     }
     __syncthreads();
+    if constexpr (GQA) tq = tq_n, hq = hq_n;
   }
   float vmul = 1.f;  // dV's store scale: the dropout keep scale
   if constexpr (DROP) vmul = P.drop_rs;
@@ -1688,6 +1765,21 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
     P.bias_sh = t.bias.sh;
     P.bias_sq = t.bias.sq;
   }
+  P.Hkv = t.kv_heads > 0 ? t.kv_heads : H;
+  if (t.kv_heads < 0 || H % P.Hkv)
+    throw std::invalid_argument("attention: grouped-query K / V heads (kv_heads) must divide the query heads H");
+  P.G = H / P.Hkv;
+  if (P.G > 1) {
+    // the GQA kernels exist without any other axis
+    if (t.drop_threshold) throw std::invalid_argument("attention: grouped-query K / V heads (kv_heads) exclude dropout");
+    if (t.kv_lens || t.q_lens)
+      throw std::invalid_argument("attention: grouped-query K / V heads (kv_heads) exclude kv_lens / q_lens");
+    if (t.seg_offsets)
+      throw std::invalid_argument("attention: grouped-query K / V heads (kv_heads) exclude packed sequences (seg_lens)");
+    if (t.bias.p) throw std::invalid_argument("attention: grouped-query K / V heads (kv_heads) exclude bias");
+    if (t.dbq || t.dbk || t.dbv)
+      throw std::invalid_argument("attention: grouped-query K / V heads (kv_heads) exclude the fused dbias");
+  }
   return P;
 }
 
@@ -1726,6 +1818,12 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
     with_features(P.drop_thr != 0, P.kv_lens || P.q_lens || packed, [&](auto dr, auto vl) {
       constexpr int DD = decltype(d)::value;
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
+      if constexpr (!DR && !VL) {
+        if (P.G > 1) {  // make_params: no dropout, lengths, packing or bias
+          hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, false, false, false, false, true>), grid, block, 0, st, P);
+          return;
+        }
+      }
       if constexpr (VL) {
         if (packed) {
           hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, DR, true, true, false>), grid, block, 0, st, P);
@@ -1766,7 +1864,8 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
   const bool drop = P.drop_thr != 0, varlen = P.kv_lens || P.q_lens || packed;
   // a second key block needs the workspace: callers that pass none keep the
   // two-kernel path
-  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv || drop || varlen || P.bias) && (Sk <= 256 || ws)) {
+  if (onepass_eligible(Sk, D, causal, t.dbq || t.dbk || t.dbv || drop || varlen || P.bias || P.G > 1) &&
+      (Sk <= 256 || ws)) {
     hipLaunchKernelGGL(attn_bwd_onepass_kernel, dim3(static_cast<unsigned>(B * H)), dim3(512), 0, st, P, ws);
     FFK_LAUNCH_CHECK("attention_bwd");
     return 1;
@@ -1779,6 +1878,16 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
     with_features(drop, varlen, [&](auto dr, auto vl) {
       constexpr int DD = decltype(d)::value;
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
+      if constexpr (!DR && !VL) {
+        if (P.G > 1) {
+          // dQ over the B * H query heads, dK/dV over the B * Hkv K / V heads
+          const unsigned nkh = static_cast<unsigned>(B * P.Hkv);
+          const dim3 gkv = causal ? dim3(nkh, nk) : dim3(nk, nkh);
+          hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, false, false, false, false, true>), gq, block, 0, st, P);
+          hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, CC, false, false, false, false, true>), gkv, block, 0, st, P);
+          return;
+        }
+      }
       if constexpr (VL) {
         if (packed) {
           hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, CC, DR, true, true, false>), gq, block, 0, st, P);

@@ -162,8 +162,9 @@ PYBIND11_MODULE(_ffkernels, m) {
   m.def("attention_fwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, uintptr_t lse, int B, int H, int Sq,
                             int Sk, int D, float scale, bool causal, uintptr_t st, uint32_t drop_t, uint64_t seed,
                             uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens, uintptr_t seg_off, int seg_M,
-                            int seg_T, py::tuple bias) {
+                            int seg_T, py::tuple bias, int kv_heads) {
     AttnTensors t;
+    t.kv_heads = kv_heads;
     set_bias(t, bias);
     t.q = tview(q);
     t.k = tview(k);
@@ -179,14 +180,15 @@ PYBIND11_MODULE(_ffkernels, m) {
         py::arg("Sq"), py::arg("Sk"), py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"),
         py::arg("drop_t") = 0, py::arg("seed") = 0, py::arg("seed_dev") = 0, py::arg("kv_lens") = 0,
         py::arg("q_lens") = 0, py::arg("seg_off") = 0, py::arg("seg_M") = 0, py::arg("seg_T") = 0,
-        py::arg("bias") = py::tuple());
+        py::arg("bias") = py::tuple(), py::arg("kv_heads") = 0);
   m.def("attention_bwd", [](py::tuple q, py::tuple k, py::tuple v, py::tuple o, py::tuple dout, py::tuple dq,
                             py::tuple dk, py::tuple dv, uintptr_t lse, uintptr_t delta, int B, int H, int Sq, int Sk,
                             int D, float scale, bool causal, uintptr_t st, uintptr_t dbq, uintptr_t dbk,
                             uintptr_t dbv, int64_t db_ld, uintptr_t ws, uint32_t drop_t, uint64_t seed,
                             uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens, uintptr_t seg_off, int seg_M,
-                            int seg_T, py::tuple bias) {
+                            int seg_T, py::tuple bias, int kv_heads) {
     AttnTensors t;
+    t.kv_heads = kv_heads;
     set_bias(t, bias);
     set_packed(t, seg_off, seg_M, seg_T);
     t.q = tview(q);
@@ -212,7 +214,7 @@ PYBIND11_MODULE(_ffkernels, m) {
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"), py::arg("dbq") = 0, py::arg("dbk") = 0,
         py::arg("dbv") = 0, py::arg("db_ld") = 0, py::arg("ws") = 0, py::arg("drop_t") = 0, py::arg("seed") = 0,
         py::arg("seed_dev") = 0, py::arg("kv_lens") = 0, py::arg("q_lens") = 0, py::arg("seg_off") = 0,
-        py::arg("seg_M") = 0, py::arg("seg_T") = 0, py::arg("bias") = py::tuple());
+        py::arg("seg_M") = 0, py::arg("seg_T") = 0, py::arg("bias") = py::tuple(), py::arg("kv_heads") = 0);
   m.def("attention_segment_offsets", [](uintptr_t seg_lens, uintptr_t seg_off, int N, int M, int T, int max_seqlen,
                                         uintptr_t st) {
     attention_segment_offsets(reinterpret_cast<const int32_t*>(seg_lens), reinterpret_cast<int32_t*>(seg_off), N, M,

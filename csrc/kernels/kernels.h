@@ -146,6 +146,15 @@ struct AttnTensors {
     int64_t sb = 0, sh = 0, sq = 0;
   };
   Bias bias = {};
+  // grouped-query attention: the head count of k / v / dk / dv (their sh
+  // strides are their own), 0 = H.  Must divide H; query head h attends over
+  // K / V head h / (H / kv_heads) (torch's enable_gqa), and dk / dv are summed
+  // over each group's query heads in fp32 inside the dK/dV kernel.  q, o,
+  // dout, dq, lse and delta keep H heads.  Always the dQ + dK/dV kernel pair;
+  // with kv_heads < H excludes dropout, kv_lens, q_lens, seg_offsets, bias and
+  // the fused dbias (std::invalid_argument).  kv_heads == H (or 0) is the
+  // call without it, on the same kernels.
+  int kv_heads = 0;
 };
 // seg_lens int32 [N, M] -> seg_off int32 [N, M, 2], both on the device: start =
 // sum of the pack's earlier clamped lengths, len clamped to [0, min(max_seqlen,
@@ -155,7 +164,7 @@ void attention_segment_offsets(const int32_t* seg_lens, int32_t* seg_off, int N,
 void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                    hipStream_t st);
 // Returns the path that ran: 1 = the one-pass kernel (D = 64, non-causal,
-// Sk <= 512, no dbias, no dropout, no key or query lengths;
+// Sk <= 512, no dbias, no dropout, no key or query lengths, kv_heads == H;
 // FFK_ATTN_BWD_ONEPASS=0, read per call, turns it off), 0 = the dQ kernel
 // (which also writes delta = rowsum(dO * O)) followed by the dK/dV kernel.
 // With Sk > 256 the one-pass kernel needs `ws`, an fp32 scratch of

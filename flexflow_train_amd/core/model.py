@@ -595,6 +595,12 @@ class FFModel:
         softmax(scale * q k^T + mask) v for ``q`` [batch, heads, Sq, D] and
         ``k`` / ``v`` [batch, heads, Sk, D]; the result is [batch, heads, Sq, D].
 
+        Grouped-query attention: ``k`` / ``v`` may be [batch, kv_heads, Sk, D]
+        with kv_heads dividing heads (multi-query attention is kv_heads = 1).
+        Query head h attends over K / V head h // (heads // kv_heads), torch's
+        ``enable_gqa`` convention; the gradients of ``k`` / ``v`` keep kv_heads
+        heads.  The head counts are read from the shapes: there is no argument.
+
         ``mask``: optional float tensor broadcastable to [batch, heads, Sq, Sk]
         (rank 4, every dim 1 or the full extent), added to the scores; -inf
         masks a pair.  A row with every key masked gives zeros (torch gives
@@ -604,7 +610,10 @@ class FFModel:
 
         bf16 on the GPU with D in {64, 128} and Sk % 4 == 0 runs on the flash
         attention kernels (no Sq x Sk tensor exists); everything else takes a
-        torch fallback of the same definition."""
+        torch fallback of the same definition.  With kv_heads < heads the
+        unmasked, undropped case runs GQA kernels in place on the kv_heads
+        storage; with a mask or dropout K / V are expanded to ``heads`` heads
+        once and the existing kernels run."""
         inputs = [q, k, v] + ([mask] if mask is not None else [])
         return self._add("SDPA", inputs, name, causal=bool(causal), dropout=float(dropout),
                          scale=float(scale or 0.0), mask=mask is not None)

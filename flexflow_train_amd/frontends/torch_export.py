@@ -420,7 +420,10 @@ class ATenImporter:
         q, k, v = (p[n] for n in ("query", "key", "value"))
         if not all(isinstance(t, FFV) and len(t.shape) == 4 for t in (q, k, v)):
             return None
-        if p.get("enable_gqa") or not (q.shape[1] == k.shape[1] == v.shape[1]):
+        # grouped-query K / V heads (enable_gqa): Hkv dividing H, read from the shapes by the operator
+        if k.shape[1] != v.shape[1] or k.shape[1] < 1 or q.shape[1] % k.shape[1]:
+            return None
+        if q.shape[1] != k.shape[1] and not p.get("enable_gqa"):
             return None
         mask, causal = p.get("attn_mask"), bool(p.get("is_causal"))
         if causal and (mask is not None or q.shape[2] != k.shape[2]):
@@ -451,12 +454,16 @@ class ATenImporter:
         """softmax(q k^T * scale + mask) v over (B, H, S, D) tensors.
 
         One SDPA node (flash attention, no [B, H, Sq, Sk] tensor) when q, k, v
-        are rank-4 FF tensors with equal head counts and the mask is absent, a
+        are rank-4 FF tensors with equal head counts (or, with enable_gqa, k
+        and v of one head count that divides q's) and the mask is absent, a
         constant, or an FF tensor that no parameter feeds: bool masks become
         additive 0 / -inf (not clamped: -inf is the kernels' "masked"),
         is_causal and dropout_p become attributes.  A mask that depends on a
         parameter (a learned position bias needs a gradient, which SDPA's mask
-        does not get), other ranks and enable_gqa keep the unfused chain below."""
+        does not get) and other ranks keep the unfused chain below.  That
+        chain does not expand K / V: a learned bias together with grouped-query
+        heads is refused by name (it used to fail in BATCHMATMUL's shape
+        inference with "batch dims mismatch")."""
         ff = self.ff
         names = ["query", "key", "value", "attn_mask", "dropout_p", "is_causal", "scale", "enable_gqa"]
         p = dict(zip(names, args))
@@ -465,6 +472,15 @@ class ATenImporter:
         if fused is not None:
             return fused
         q, k, v = (self._ffv(p[n], node) for n in ("query", "key", "value"))
+        if p.get("enable_gqa") and len(q.shape) == 4 and len(k.shape) == 4 and q.shape[1] != k.shape[1]:
+            m = p.get("attn_mask")
+            if isinstance(m, Param) or (isinstance(m, FFV) and m.from_param):
+                raise NotImplementedError(f"{name}: scaled_dot_product_attention: enable_gqa with a learned attention "
+                                          "bias (a mask that a parameter feeds) is not supported: the unfused lowering "
+                                          "does not expand K / V; expand them in the module (repeat_interleave)")
+            raise NotImplementedError(f"{name}: scaled_dot_product_attention with enable_gqa needs rank-4 q / k / v, "
+                                      f"H % Hkv == 0 and equal k / v head counts, got q {tuple(q.shape)}, "
+                                      f"k {tuple(k.shape)}, v {tuple(v.shape)}")
         d = q.shape[-1]
         scale = p.get("scale")
         scale = 1.0 / math.sqrt(d) if scale is None else float(scale)

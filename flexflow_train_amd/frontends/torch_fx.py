@@ -91,8 +91,8 @@ class PyTorchModel:
         self.modules = dict(self.model.named_modules())
         if self.graph is not None:
             # F.scaled_dot_product_attention maps to one SDPA node here; a call
-            # that does not fit it (a mask that a parameter feeds, grouped-query
-            # heads) has its unfused lowering in the torch.export path
+            # that does not fit it (a mask that a parameter feeds) has its
+            # unfused lowering in the torch.export path
             why = next((w for w in (_sdpa_unfit(self, n) for n in self.graph.graph.nodes) if w), None)
             if why:
                 self.graph, self.trace_error = None, NotImplementedError(why)
@@ -317,8 +317,7 @@ def _sdpa_unfit(pm, node) -> Optional[str]:
     if node.op != "call_function" or node.target is not F.scaled_dot_product_attention:
         return None
     p = _sdpa_args(node)
-    if p.get("enable_gqa"):
-        return "scaled_dot_product_attention with enable_gqa: imported through torch.export (unfused)"
+    # enable_gqa fits: the SDPA operator reads Hkv from the shapes (its shape inference checks H % Hkv)
     mask = p.get("attn_mask")
     if isinstance(mask, torch.fx.Node) and _param_fed(pm, mask, {}):
         return ("scaled_dot_product_attention with a mask that depends on a parameter: imported through "

@@ -510,6 +510,30 @@ def _attn_bias(bias, q, Sq, Sk, causal=False, kv_lens=None, q_lens=None, seg_len
     return (bias.data_ptr(), strides[0], strides[1], strides[2]), bias
 
 
+def _attn_gqa(q, k, v, dropout_p=0.0, kv_lens=None, q_lens=None, seg_lens=None, bias=None, dbias=None):
+    """K / V head count of an attention call if it takes the GQA kernels
+    (``k.shape[2]`` < H), else 0.  Every rule of the GQA kernels is checked
+    here, by name, before anything is launched; shapes that are wrong for
+    other reasons are left to the caller's "q/k/v shape mismatch"."""
+    if k.dim() != 4 or v.dim() != 4:
+        return 0
+    H, Hkv = q.shape[2], k.shape[2]
+    if Hkv == H and v.shape[2] == H:
+        return 0
+    if v.shape[2] != Hkv:
+        raise ValueError(f"attention: grouped-query K / V heads: v has {v.shape[2]} heads, k has {Hkv}")
+    if Hkv < 1 or H % Hkv:
+        raise ValueError(f"attention: grouped-query K / V heads: H = {H} query heads are not a multiple of "
+                         f"Hkv = {Hkv} K / V heads (H % Hkv != 0)")
+    for what, on in (("dropout_p", float(dropout_p) > 0.0), ("kv_lens", kv_lens is not None),
+                     ("q_lens", q_lens is not None), ("packed sequences (seg_lens)", seg_lens is not None),
+                     ("bias", bias is not None), ("the fused dbias", dbias is not None)):
+        if on:
+            raise ValueError(f"attention: grouped-query K / V heads (Hkv = {Hkv} < H = {H}) cannot be combined with "
+                             f"{what}; expand K / V to H heads for that call")
+    return Hkv
+
+
 def attention_segment_offsets(seg_lens, T: int, max_seqlen: Optional[int] = None):
     """Clamped (start, len) of every segment of a packed batch: int32
     [N, M, 2] from ``seg_lens`` int32 [N, M], computed on the device (no host
@@ -574,6 +598,14 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     strides, e.g. slices of a packed [B, S, 3, H, D] QKV buffer).
     Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain).
 
+    Grouped-query attention: k and v may be [B, Sk, Hkv, D] views with Hkv
+    dividing H (read from ``k.shape[2]``; v must have k's head count).  Query
+    head h attends over K / V head h // (H // Hkv), torch's ``enable_gqa``
+    convention, in place on the Hkv-head storage; o and lse keep H heads and
+    equal those of a call on K / V expanded to H heads bit for bit.  Excludes
+    ``dropout_p``, ``kv_lens`` / ``q_lens``, ``seg_lens`` and ``bias``
+    (ValueError).  Hkv == H is the call without it, on the same kernels.
+
     ``dropout_p`` > 0: dropout on the attention probabilities inside the
     kernel; the mask is that of ``ops.attention.attention_dropout_mask`` for
     the seed ``seed + seed_dev[0]`` (``seed_dev``: optional 1-element int64
@@ -620,6 +652,19 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     Sk = k.shape[1]
     if D not in (64, 128):
         raise ValueError("attention: head dim must be 64 or 128")
+    Hkv = _attn_gqa(q, k, v, dropout_p, kv_lens, q_lens, seg_lens, bias)
+    if Hkv:
+        if k.shape != (B, Sk, Hkv, D) or v.shape != (B, Sk, Hkv, D):
+            raise ValueError("attention: q/k/v shape mismatch")
+        if out is None:
+            out = torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
+        lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
+        sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+        ext().attention_fwd(_view4(q), _view4(k), _view4(v), _view4(out), lse.data_ptr(), B, H, Sq, Sk, D, sc,
+                            bool(causal), _stream(), kv_heads=Hkv)
+        STATS["attention_gqa"] += 1
+        STATS["attention_fwd"] += 1
+        return out, lse
     bview, bkeep = _attn_bias(bias, q, Sq, Sk, causal, kv_lens, q_lens, seg_lens)
     if seg_lens is not None:
         pk = _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens)
@@ -671,9 +716,35 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     dv are written by its own workgroups and the rows past a pack's last
     segment as zeros.  ``bias``: the forward call's score bias (always path 0,
     no ``dbias``); a row with every key masked gets dq = 0 and adds nothing to
-    dk / dv, and no gradient is produced for the bias itself."""
+    dk / dv, and no gradient is produced for the bias itself.
+
+    Grouped-query attention: with k / v of Hkv < H heads (see
+    ``attention_fwd``) dk / dv must be [B, Sk, Hkv, D]; each is the sum over
+    its group's query heads, accumulated in fp32 inside the dK/dV kernel and
+    rounded to bf16 once.  Always path 0; excludes ``dbias`` and everything
+    the forward excludes."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
+    Hkv = _attn_gqa(q, k, v, dropout_p, kv_lens, q_lens, seg_lens, bias, dbias)
+    if Hkv:
+        if k.shape != (B, Sk, Hkv, D) or v.shape != (B, Sk, Hkv, D):
+            raise ValueError("attention: q/k/v shape mismatch")
+        for name, t, shp in (("o", o, (B, Sq, H, D)), ("do", do, (B, Sq, H, D)), ("dq", dq, (B, Sq, H, D)),
+                             ("dk", dk, (B, Sk, Hkv, D)), ("dv", dv, (B, Sk, Hkv, D))):
+            if tuple(t.shape) != shp:
+                raise ValueError(f"attention_bwd: {name} has shape {tuple(t.shape)}, expected {shp}"
+                                 + (f" (grouped-query: dk / dv take the Hkv = {Hkv} K / V heads)"
+                                    if name in ("dk", "dv") else ""))
+        if lse.shape != (B, H, Sq) or lse.dtype != torch.float32 or not lse.is_contiguous():
+            raise ValueError("attention_bwd: bad lse")
+        delta = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
+        sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
+        path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
+                                   _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
+                                   _stream(), kv_heads=Hkv)
+        STATS["attention_gqa"] += 1
+        STATS["attention_bwd"] += 1
+        return path
     bview, bkeep = _attn_bias(bias, q, Sq, Sk, causal, kv_lens, q_lens, seg_lens, dbias)
     pk = None
     if seg_lens is not None:

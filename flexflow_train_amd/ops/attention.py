@@ -616,6 +616,11 @@ def _flash_bias_ok(mask, Sk) -> bool:
     return mask.data_ptr() % 16 == 0
 
 
+def _expand_kv(x, G: int):
+    """[B, Hkv, S, D] -> [B, Hkv * G, S, D], K / V head j serving query heads j * G .. (torch's enable_gqa)."""
+    return x if G == 1 else x.repeat_interleave(G, dim=1)
+
+
 @register("SDPA")
 class ScaledDotProductAttentionOp(OpImpl):
     """softmax(scale * q k^T + mask) v without projections.
@@ -634,7 +639,19 @@ class ScaledDotProductAttentionOp(OpImpl):
     from the operator's device step counter like MULTIHEAD_ATTENTION, so a
     captured step gets a new mask per replay.  Everything else (CPU, fp32,
     other head dims, Sk % 4 != 0, odd mask strides) runs _torch_attention,
-    the same definition in torch."""
+    the same definition in torch.
+
+    Grouped-query attention: k / v may have Hkv heads, [B, Hkv, Sk, D], with
+    Hkv dividing H (read from the shapes; no attribute).  Query head h attends
+    over K / V head h // (H // Hkv), torch's ``enable_gqa``; dk / dv come back
+    with Hkv heads, summed over each group.  Without a mask or dropout the
+    flash case runs the GQA kernels in place on the Hkv-head storage.  With a
+    mask the BIAS kernels take, or with dropout, K and V are expanded to H
+    heads once (G times the K / V bytes, still no Sq x Sk tensor), the
+    existing kernels run as for Hkv == H, and dk / dv are reduced over the
+    group in fp32 and cast once.  Everything else runs _torch_attention on
+    K / V expanded inside the autograd graph.  The dropout mask and the
+    fallback's mask keep H as their head count."""
 
     def forward(self, ctx: OpContext, inputs, weights):
         q, k, v = inputs[:3]
@@ -643,6 +660,14 @@ class ScaledDotProductAttentionOp(OpImpl):
             raise ValueError(f"{ctx.name}: q / k / v must be [batch, heads, seq, head_dim]")
         B, H, Sq, D = q.shape
         Sk = k.shape[2]
+        Hkv = k.shape[1]
+        if v.shape[1] != Hkv:
+            raise ValueError(f"{ctx.name}: k has {Hkv} heads and v has {v.shape[1]}: grouped-query K / V need "
+                             "equal head counts")
+        if Hkv < 1 or H % Hkv:
+            raise ValueError(f"{ctx.name}: {H} query heads are not a multiple of {Hkv} K / V heads "
+                             "(grouped-query attention needs H % Hkv == 0)")
+        G = H // Hkv
         causal = bool(ctx.a("causal", False))
         if causal and mask is not None:
             raise ValueError(f"{ctx.name}: causal cannot be combined with a mask")
@@ -670,20 +695,26 @@ class ScaledDotProductAttentionOp(OpImpl):
                      and (mask is None or _flash_bias_ok(mask, Sk)))
         if use_flash:
             q, k, v = (t if t.stride(3) == 1 and t.is_contiguous() else t.contiguous() for t in (q, k, v))
+            if G > 1 and (mask is not None or drop):
+                # the BIAS / DROP kernels have no GQA form: K / V expanded to H
+                # heads once, kept for the backward
+                k, v = k.repeat_interleave(G, dim=1), v.repeat_interleave(G, dim=1)
             o = torch.empty(B, H, Sq, D, device=q.device, dtype=q.dtype)
             kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
             _, lse = K.attention_fwd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal=causal,
                                      scale=scale, out=o.transpose(1, 2), bias=mask, **kw)
         else:
-            o = _torch_attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal, scale,
+            o = _torch_attention(q.transpose(1, 2), _expand_kv(k, G).transpose(1, 2),
+                                 _expand_kv(v, G).transpose(1, 2), causal, scale,
                                  _fallback_mask(drop, B, H, Sq, Sk), bias=mask).transpose(1, 2).contiguous()
             lse = None
-        return [o], (q, k, v, mask, o, lse, causal, scale, drop)
+        return [o], (q, k, v, mask, o, lse, causal, scale, drop, Hkv)
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
-        q, k, v, mask, o, lse, causal, scale, drop = saved
+        q, k, v, mask, o, lse, causal, scale, drop, Hkv = saved
         B, H, Sq, D = q.shape
         Sk = k.shape[2]
+        G = H // Hkv
         do = grad_outputs[0]
         tail = [None] if mask is not None else []   # the mask gets no gradient
         if lse is not None:
@@ -693,9 +724,15 @@ class ScaledDotProductAttentionOp(OpImpl):
             t = lambda x: x.transpose(1, 2)
             K.attention_bwd(t(q), t(k), t(v), t(o), lse, t(do), t(dq), t(dk), t(dv), causal=causal, scale=scale,
                             bias=mask, **kw)
+            if k.shape[1] != Hkv:
+                # the expanded path: the group sum in fp32, one cast
+                dk = dk.view(B, Hkv, G, Sk, D).sum(2, dtype=torch.float32).to(q.dtype)
+                dv = dv.view(B, Hkv, G, Sk, D).sum(2, dtype=torch.float32).to(q.dtype)
         else:
             qf, kf, vf = (x.detach().float().requires_grad_(True) for x in (q, k, v))
-            ref = _torch_attention(qf.transpose(1, 2), kf.transpose(1, 2), vf.transpose(1, 2), causal, scale,
+            # K / V expanded inside the graph: autograd does the group sum
+            ref = _torch_attention(qf.transpose(1, 2), _expand_kv(kf, G).transpose(1, 2),
+                                   _expand_kv(vf, G).transpose(1, 2), causal, scale,
                                    _fallback_mask(drop, B, H, Sq, Sk), bias=mask)
             ref.float().backward(do.float().transpose(1, 2))
             dq, dk, dv = (x.grad.to(do.dtype) for x in (qf, kf, vf))

@@ -11,6 +11,8 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
     python tools/attn_time.py --packed [--dropout 0.1]                (packed sequences against the padded batch)
     python tools/attn_time.py --bias key|full                         (additive mask / bias against no bias, kv_lens
                                                                        and the unfused operator chain)
+    python tools/attn_time.py --gqa G                                 (grouped-query K / V heads, H / G of them,
+                                                                       against the expanded call and the H-head call)
 
 --d128 appends two D = 128 shapes to whichever mode is run.
 """
@@ -339,7 +341,83 @@ def bias_ab(kind, iters, rounds=5, seed=0):
         print(json.dumps(rec), flush=True)
 
 
+GQA_SHAPES = {"b4-h32-d128-s2048-causal": (4, 2048, 32, 128, True), "b8-h16-d64-s2048-causal": (8, 2048, 16, 64, True)}
+
+
+def gqa_ab(G, iters, rounds=5):
+    """Interleaved same-process timing of the forward and the backward with
+    Hkv = H / G K / V heads, three forms per shape in every round:
+      gqa       the GQA kernels in place on [B, S, Hkv, D] K / V;
+      expanded  what a caller had to do before: K / V copied out to H heads
+                (repeat_interleave), the existing kernels, and in the backward
+                the fp32 group sum of dK / dV and its cast (all of it timed);
+      plain_1 / plain_2  the H-head call of the same flops, twice: the ceiling
+                and its own run-to-run spread.
+    A shape whose H is no multiple of G is skipped.  `dkdv_workgroups_*`: the
+    dK/dV kernel's grid, B * heads * ceil(S / 128), against the 256 CUs."""
+    import statistics
+    for name, (B, S, H, D, causal) in GQA_SHAPES.items():
+        if H % G:
+            print(json.dumps({"shape": name, "G": G, "skipped": f"H = {H} is no multiple of G"}), flush=True)
+            continue
+        Hkv = H // G
+        g = torch.Generator(device="cuda").manual_seed(0)
+        q, do = (torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g) for _ in range(2))
+        k, v = (torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, generator=g) for _ in range(2))
+        kp, vp = (torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g) for _ in range(2))
+        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+        dkp, dvp = torch.empty_like(kp), torch.empty_like(vp)
+        o = torch.empty_like(q)
+
+        def exp_fwd():
+            ke, ve = k.repeat_interleave(G, dim=2), v.repeat_interleave(G, dim=2)
+            return ke, ve, K.attention_fwd(q, ke, ve, causal=causal, out=o)[1]
+
+        def exp_bwd(ke, ve, lse):
+            K.attention_bwd(q, ke, ve, o, lse, do, dq, dkp, dvp, causal=causal)
+            return (dkp.view(B, S, Hkv, G, D).sum(3, dtype=torch.float32).to(torch.bfloat16),
+                    dvp.view(B, S, Hkv, G, D).sum(3, dtype=torch.float32).to(torch.bfloat16))
+
+        forms = ("gqa", "expanded", "plain_1", "plain_2")
+        t = {}
+        for _ in range(rounds):
+            for tag in forms:
+                if tag == "gqa":
+                    _, lse = K.attention_fwd(q, k, v, causal=causal, out=o)
+                    fwd = lambda: K.attention_fwd(q, k, v, causal=causal, out=o)  # noqa: E731
+                    bwd = lambda: K.attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=causal)  # noqa: E731
+                elif tag == "expanded":
+                    ke, ve, lse = exp_fwd()
+                    fwd = exp_fwd
+                    bwd = lambda: exp_bwd(ke, ve, lse)  # noqa: E731
+                else:
+                    _, lse = K.attention_fwd(q, kp, vp, causal=causal, out=o)
+                    fwd = lambda: K.attention_fwd(q, kp, vp, causal=causal, out=o)  # noqa: E731
+                    bwd = lambda: K.attention_bwd(q, kp, vp, o, lse, do, dq, dkp, dvp, causal=causal)  # noqa: E731
+                t.setdefault(("fwd", tag), []).append(_time(fwd, iters))
+                t.setdefault(("bwd", tag), []).append(_time(bwd, iters))
+        fl = 4 * B * H * S * S * D * (0.5 if causal else 1.0)
+        med = {key: statistics.median(x) for key, x in t.items()}
+        nkb = (S + 127) // 128
+        rec = {"shape": name, "G": G, "Hkv": Hkv, "iters": iters, "rounds": rounds,
+               "dkdv_workgroups_gqa": B * Hkv * nkb, "dkdv_workgroups_plain": B * H * nkb, "cus": 256,
+               "kv_bytes_gqa": 2 * B * S * Hkv * D * 2, "kv_bytes_expanded": 2 * B * S * H * D * 2}
+        for which, mul in (("fwd", 1.0), ("bwd", 2.5)):
+            for tag in forms:
+                xs = t[(which, tag)]
+                rec[f"{which}_ms_{tag}"] = round(med[(which, tag)], 4)
+                rec[f"{which}_tflops_{tag}"] = round(mul * fl / med[(which, tag)] / 1e9, 1)
+                rec[f"{which}_spread_{tag}"] = round((max(xs) - min(xs)) / med[(which, tag)], 4)
+                rec[f"{which}_rounds_{tag}"] = [round(x, 4) for x in xs]
+            rec[f"{which}_gqa_over_plain"] = round(med[(which, "gqa")] / med[(which, "plain_1")], 3)
+            rec[f"{which}_gqa_over_expanded"] = round(med[(which, "gqa")] / med[(which, "expanded")], 3)
+            rec[f"{which}_plain_2_over_plain_1"] = round(med[(which, "plain_2")] / med[(which, "plain_1")], 3)
+        print(json.dumps(rec), flush=True)
+
+
 def main():
+    if "--gqa" in sys.argv:            # grouped-query K / V heads against the expanded and the H-head call
+        return gqa_ab(int(sys.argv[sys.argv.index("--gqa") + 1]), 200)
     if "--bias" in sys.argv:           # additive mask / bias against no bias, kv_lens and the unfused chain
         kind = sys.argv[sys.argv.index("--bias") + 1]
         if kind not in ("key", "full"):
