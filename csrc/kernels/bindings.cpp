@@ -355,7 +355,7 @@ PYBIND11_MODULE(_ffkernels, m) {
   m.def("gemmp", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre, uintptr_t aux,
                     uintptr_t dbias, int M, int N, int K, int lda, int ldb, int ldc, bool ta, bool tb, int act,
                     bool act_bwd, float alpha, float beta, int out_f32, int splits, uintptr_t ws, uintptr_t st,
-                    int dbg, int variant) {
+                    int dbg, int variant, uintptr_t bsum) {
     GemmPParams p;
     p.A = P(A); p.B = P(B); p.C = P(C); p.bias = P(bias); p.pre = P(pre); p.aux = P(aux); p.dbias = F(dbias);
     p.workspace = F(ws);
@@ -363,11 +363,13 @@ PYBIND11_MODULE(_ffkernels, m) {
     p.act = act; p.act_bwd = act_bwd; p.alpha = alpha; p.beta = beta; p.out_f32 = out_f32; p.splits = splits;
     p.dbg = dbg;
     p.variant = variant;
+    p.bsum = F(bsum);
     gemmp_bf16(p, S(st));
   }, py::arg("A"), py::arg("B"), py::arg("C"), py::arg("bias"), py::arg("pre"), py::arg("aux"), py::arg("dbias"),
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("lda"), py::arg("ldb"), py::arg("ldc"), py::arg("ta"),
         py::arg("tb"), py::arg("act"), py::arg("act_bwd"), py::arg("alpha"), py::arg("beta"), py::arg("out_f32"),
-        py::arg("splits"), py::arg("ws"), py::arg("st"), py::arg("dbg") = 0, py::arg("variant") = 0);
+        py::arg("splits"), py::arg("ws"), py::arg("st"), py::arg("dbg") = 0, py::arg("variant") = 0,
+        py::arg("bsum") = 0);
   m.def("gemm256_supported", &gemm256_supported);
   m.def("gemm256", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre, int M, int N, int K,
                       int lda, int ldb, int ldc, bool ta, bool tb, int act, float alpha, float beta, int out_f32,

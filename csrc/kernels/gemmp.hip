@@ -540,6 +540,9 @@ void gemmp_bf16(const GemmPParams& p, hipStream_t st) {
     throw std::invalid_argument("gemmp: the activation-gradient epilogue writes bf16, no beta / bias / pre");
   if (p.dbias && epi != kEpiDact) throw std::invalid_argument("gemmp: dbias needs the activation-gradient epilogue");
   if (epi == kEpiBiasAct && p.out_f32) throw std::invalid_argument("gemmp: bias / activation epilogue writes bf16");
+  if (p.bsum && !(p.variant == 6 && small && gemmt_supported(p)))
+    throw std::invalid_argument("gemmp: bsum needs variant 6 with 32-bit addressable operands");
+  if (p.bsum && (reinterpret_cast<uintptr_t>(p.bsum) & 3)) throw std::invalid_argument("gemmp: bsum must be fp32-aligned");
   if (p.variant == 11 && splits == 1 && gemmpp_supported(p)) {
     gemmpp_launch(p, st);
     return;

@@ -66,6 +66,7 @@ struct GemmTArgs {
   int act, act_bwd, out_f32, splits;
   unsigned bytesA, bytesB;
   int dbg;   // ablation bits (timing experiments, tools/gemm_ablate.py)
+  float* bsum;   // gemmt_kk_kernel<..., BS = true>: += column sums of B
 };
 
 typedef float f32x2t __attribute__((ext_vector_type(2)));
@@ -814,7 +815,22 @@ __device__ __forceinline__ void kk_for(F&& f, std::integer_sequence<int, I...>) 
 // (MI355X_MICROARCH.md cycle constants, 'LDS-DMA piece issue cost'); a
 // buffer_load + ds_write_b128 pair ~20, inside the MFMA gaps, and the loads
 // get a whole K-tile (not one phase) to land.
-template <bool TA, int EPI, int ACT, int SCH = 0, bool TB = false, bool RS = false>
+// BS (A^T B only): also bsum[n] += sum_k B[k][n] over the K range this split
+// walks, i.e. the bias gradient 1^T g beside the weight gradient x^T g, from
+// the B fragments that are in registers anyway: mfma(B fragment, ones) gives
+// D[n][m] = sum_k B[k][n] in every column m (a product with 1.0 is exact, the
+// sum is fp32), and a NaN in a padded neighbour column stays in its own row
+// n >= N, which is never stored.  The two wave rows of a workgroup hold the
+// same B fragments and the gm row tiles of one (column tile, split) stream
+// the same B tile, so wave row wm takes the blocks nb = 4 wm .. 4 wm + 3 and
+// row tile i only the 32-deep k-steps whose global index is i (mod gm): each
+// (k-step, column) is summed once across the grid, by 4 extra MFMAs in one of
+// every gm k-steps of 64 (a wave-uniform, scalar branch).  The partial sums
+// of the gm * splits workgroups meet in fp32 atomicAdds, so the summation
+// order (not the set of terms) differs from run to run, as kEpiDact's dbias
+// does.  The main accumulators see the same MFMAs in the same order: C and
+// the split-K slabs are bit-identical to BS = false.
+template <bool TA, int EPI, int ACT, int SCH = 0, bool TB = false, bool RS = false, bool BS = false>
 __global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemmt_kk_kernel(
     GemmTArgs g) {
   constexpr int SA = TA ? KK_PT : 2 * HALF;   // A tile bytes per buffer
@@ -939,6 +955,60 @@ __global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, 
   bf16x8 fa[8], fbx[8], fby[8];
   constexpr auto S8 = std::make_integer_sequence<int, 8>{};
 
+  // BS: column-sum accumulators of this wave's 4 blocks; bcnt = (global
+  // k-step index - row tile) mod gm, this workgroup sums when it is 0
+  static_assert(!BS || (TA && !TB), "bsum: A^T B only");
+  f32x4t accS[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) accS[j] = f32x4t{};
+  int bcnt = BS ? (2 * kt0 + gm - m0 / TM) % gm : 0;
+  // The four MFMAs are issued from asm in their VGPR form: the 256 AGPRs are
+  // the main accumulators', and with the builtin hipcc puts these in AGPRs
+  // too and shuttles 32 main accumulators through VGPRs in every phase.  The
+  // string carries its own wait states (hipcc pads nothing inside asm): two
+  // ahead of the first operand read, twelve after the last MFMA before
+  // anything else may touch its destination (they pass under the MFMAs'
+  // own 64 cycles).
+  constexpr __bf16 kOne = 1.0f;
+  bf16x8 ones{kOne, kOne, kOne, kOne, kOne, kOne, kOne, kOne};
+  if constexpr (BS) {
+    asm volatile("" : "+v"(ones));   // one register quad set ahead of the loop
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(accS[j]));
+  }
+  auto bsum_step = [&](const bf16x8 (&fin)[8]) __attribute__((always_inline)) {
+    if constexpr (BS) {
+      __builtin_amdgcn_sched_barrier(0);
+      // the wave row picks its four blocks by a scalar branch inside the
+      // string: one statement, so the sums stay in one register set (two
+      // statements under if / else made hipcc copy them on every pass)
+      if (bcnt == 0)
+        asm volatile(
+            "s_nop 1\n\t"
+            "s_cmp_lg_u32 %13, 0\n\t"
+            "s_cbranch_scc1 1f\n\t"
+            "v_mfma_f32_16x16x32_bf16 %0, %4, %12, %0\n\t"
+            "v_mfma_f32_16x16x32_bf16 %1, %5, %12, %1\n\t"
+            "v_mfma_f32_16x16x32_bf16 %2, %6, %12, %2\n\t"
+            "v_mfma_f32_16x16x32_bf16 %3, %7, %12, %3\n\t"
+            "s_branch 2f\n"
+            "1:\n\t"
+            "v_mfma_f32_16x16x32_bf16 %0, %8, %12, %0\n\t"
+            "v_mfma_f32_16x16x32_bf16 %1, %9, %12, %1\n\t"
+            "v_mfma_f32_16x16x32_bf16 %2, %10, %12, %2\n\t"
+            "v_mfma_f32_16x16x32_bf16 %3, %11, %12, %3\n"
+            "2:\n\t"
+            "s_nop 7\n\t"
+            "s_nop 3"
+            : "+v"(accS[0]), "+v"(accS[1]), "+v"(accS[2]), "+v"(accS[3])
+            : "v"(fin[0]), "v"(fin[1]), "v"(fin[2]), "v"(fin[3]), "v"(fin[4]), "v"(fin[5]), "v"(fin[6]),
+              "v"(fin[7]), "v"(ones), "s"(wm)
+            : "scc");
+      bcnt = bcnt + 1 == gm ? 0 : bcnt + 1;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
   auto readA = [&](auto KSC, auto MBC, unsigned base) __attribute__((always_inline)) -> bf16x8 {
     constexpr int ks = decltype(KSC)::value, mb = decltype(MBC)::value;
     if constexpr (TA) return kk_frag<ks, mb>(base);
@@ -1054,6 +1124,7 @@ __global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, 
     const unsigned ka = static_cast<unsigned>(kt0 + kt + 2) * kstepA;
     const unsigned kb = static_cast<unsigned>(kt0 + kt + 2) * kstepB;
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    bsum_step(fbx);
     // phase A: k-step 0 (fa, fbx) | read k-step 1 of the current buffer into (fa, fby)
     kk_for([&](auto MB) __attribute__((always_inline)) {
       constexpr int mb = decltype(MB)::value;
@@ -1075,6 +1146,7 @@ __global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, 
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // k-step 1 reads (RS: and the staging writes) done
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
+    bsum_step(fby);
     // phase B: k-step 1 (fa, fby) | read k-step 0 of the next buffer into (fa, fbx),
     // DMA tile kt+2 into the current one (its reads retired at the barrier)
     kk_for([&](auto MB) __attribute__((always_inline)) {
@@ -1102,6 +1174,19 @@ __global__ __launch_bounds__(NTHREADS, 1) __attribute__((amdgpu_waves_per_eu(1, 
 #pragma unroll
     for (int j = 0; j < 8; ++j) if (0) asm volatile("" : "+a"(acc[i][j]));
   epilogue<EPI, ACT, false, false>(g, acc, m0, n0, split, wm, wn, lane, nullptr);
+  if constexpr (BS) {
+    // accS[j][e] is column n0 + wn*128 + (4 wm + j)*16 + 4 (lane >> 4) + e, the
+    // same value in all 16 lanes of a row group: lane & 15 picks (j, e), one
+    // atomicAdd per column per wave
+    const int idx = lane & 15;
+    float v = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v = idx == 4 * j + e ? accS[j][e] : v;
+    const int n = n0 + wn * 128 + (4 * wm + (idx >> 2)) * 16 + 4 * (lane >> 4) + (idx & 3);
+    if (n < g.N) atomicAdd(g.bsum + n, v);
+  }
 }
 
 // Persistent form (variant 5): one workgroup per CU walks its work items
@@ -1364,6 +1449,25 @@ void launch_t(const GemmTArgs& g, dim3 grid, dim3 block, int epi, int act, hipSt
   }
 }
 
+// A^T B with the column sums of B (bsum): the LDS-DMA form, interleaved schedule
+void launch_kk_bsum(const GemmTArgs& g, dim3 grid, dim3 block, int epi, hipStream_t st) {
+  switch (epi) {
+    case kEpiPlain:
+      hipLaunchKernelGGL((gemmt_kk_kernel<true, kEpiPlain, 0, 1, false, false, true>), grid, block, 0, st, g);
+      break;
+    case kEpiSplit:
+      hipLaunchKernelGGL((gemmt_kk_kernel<true, kEpiSplit, 0, 1, false, false, true>), grid, block, 0, st, g);
+      break;
+    case kEpiGeneral:
+      hipLaunchKernelGGL((gemmt_kk_kernel<true, kEpiGeneral, 0, 1, false, false, true>), grid, block, 0, st, g);
+      break;
+    case kEpiAccum:
+      hipLaunchKernelGGL((gemmt_kk_kernel<true, kEpiAccum, 0, 1, false, false, true>), grid, block, 0, st, g);
+      break;
+    default: throw std::invalid_argument("gemmt: bsum with a bias / activation epilogue");
+  }
+}
+
 template <bool TA, int SCH, bool TB, bool RS = false>
 void launch_kk_s(const GemmTArgs& g, dim3 grid, dim3 block, int epi, int act, hipStream_t st) {
   switch (epi * 8 + act) {
@@ -1461,7 +1565,7 @@ void gemmt_launch(const GemmPParams& p, int splits, int stage_mode, hipStream_t 
               static_cast<const bf16*>(p.bias), static_cast<bf16*>(p.pre), static_cast<const bf16*>(p.aux), p.dbias,
               p.M, p.N, p.K, p.lda, p.ldb, p.ldc, p.alpha, p.beta, p.act, p.act_bwd ? 1 : 0, p.out_f32, splits,
               bytes(p.trans_a ? p.K : p.M, p.lda, p.trans_a ? p.M : p.K),
-              bytes(p.trans_b ? p.N : p.K, p.ldb, p.trans_b ? p.K : p.N), p.dbg};
+              bytes(p.trans_b ? p.N : p.K, p.ldb, p.trans_b ? p.K : p.N), p.dbg, p.bsum};
   const int items = ((p.M + TM - 1) / TM) * ((p.N + TN - 1) / TN) * splits;
   dim3 grid(items), block(NTHREADS);
   const int epi = splits > 1                        ? kEpiSplit
@@ -1473,6 +1577,13 @@ void gemmt_launch(const GemmPParams& p, int splits, int stage_mode, hipStream_t 
                   : (p.out_f32 || p.beta != 0.f || p.alpha != 1.f) ? kEpiGeneral
                                                                    : kEpiPlain;
   const int L = p.K / TK / splits;
+  if (p.bsum) {
+    if (stage_mode != 3 || !p.trans_a || p.trans_b || p.dbg || !kk_enabled())
+      throw std::invalid_argument("gemmt: bsum needs A^T B on variant 6 (padded-image LDS-DMA kernel)");
+    launch_kk_bsum(g, grid, block, epi, st);
+    FFK_LAUNCH_CHECK("gemmt");
+    return;
+  }
   if (stage_mode == 2 && L >= 2 && (p.K / TK) % splits == 0) {
     static int n_cu = [] {
       int dev = 0, n = 0;

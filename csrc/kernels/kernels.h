@@ -207,6 +207,8 @@ struct GemmPParams {
   void* pre = nullptr;          // pre-activation out, bf16 (ldc)
   const void* aux = nullptr;    // pre-activation in for act_bwd, bf16 (ldc)
   float* dbias = nullptr;       // += column sums of the result (fp32 atomics)
+  float* bsum = nullptr;        // [N] += column sums of operand B over K (fp32 atomics): A^T B on
+                                // variant 6 only, any split count (the bias gradient beside dW)
   float* workspace = nullptr;   // split-K fp32 [splits][M][N]
   int M = 0, N = 0, K = 0, lda = 0, ldb = 0, ldc = 0;
   bool trans_a = false, trans_b = false;

@@ -939,12 +939,18 @@ def gemmp_supported(a, b, trans_a=False, trans_b=False) -> bool:
 
 
 def gemmp(a, b, trans_a=False, trans_b=False, bias=None, act="none", alpha=1.0, beta=0.0, out=None,
-          out_dtype=None, pre=None, aux=None, act_bwd=False, dbias=None, splits=1, _dbg=0, variant=0):
+          out_dtype=None, pre=None, aux=None, act_bwd=False, dbias=None, splits=1, _dbg=0, variant=0, bsum=None):
     """Phase-pipelined 256x256 MFMA GEMM (csrc/kernels/gemmp.hip):
     C = epi(alpha * op(a) op(b)); epi = [+bias] [pre := .] [act(.) or, with
     ``act_bwd``, . * act'(aux)] [dbias += colsum] [+ beta * C].  Split-K
     (``splits`` > 1): fp32 partial slabs + a reduce pass, plain epilogue only.
-    ``variant`` 1 runs the same pipeline on 16x16x32 MFMAs (gemmq.hip)."""
+    ``variant`` 1 runs the same pipeline on 16x16x32 MFMAs (gemmq.hip).
+    ``dbias`` (fp32 [N]) += the column sums of the OUTPUT (activation-gradient
+    epilogue, forces ``splits`` = 1); ``bsum`` (fp32 [N]) += the column sums of
+    the OPERAND ``b`` over K: the bias gradient beside a weight gradient
+    ``a^T b``, taken from the fragments the GEMM streams anyway (``trans_a``
+    only, ``variant`` 6, plain epilogues, any ``splits``).  Both accumulate
+    with fp32 atomics: the summation order varies from run to run."""
     if not gemmp_supported(a, b, trans_a, trans_b):
         raise ValueError("gemmp: unsupported operands (bf16, 16-B aligned, K % 64, dims % 8)")
     M, K = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
@@ -963,6 +969,11 @@ def gemmp(a, b, trans_a=False, trans_b=False, bias=None, act="none", alpha=1.0, 
                 raise ValueError(f"gemmp: {nm} needs a dense output")
     if dbias is not None:
         _check(dbias, "dbias", torch.float32, N)
+    if bsum is not None:
+        _check(bsum, "bsum", torch.float32, N, aligned=False)
+        if not trans_a or trans_b or variant != 6 or bias is not None or pre is not None or act != "none" \
+                or dbias is not None:
+            raise ValueError("gemmp: bsum needs a^T b on variant 6 with a plain epilogue")
     if act_bwd and (aux is None or act == "none"):
         raise ValueError("gemmp: act_bwd needs aux and an activation")
     s = max(1, int(splits))
@@ -974,7 +985,7 @@ def gemmp(a, b, trans_a=False, trans_b=False, bias=None, act="none", alpha=1.0, 
     ext().gemmp(a.data_ptr(), b.data_ptr(), out.data_ptr(), _p(bias), _p(pre), _p(aux), _p(dbias), M, N, K,
                 a.stride(0), b.stride(0), out.stride(0), bool(trans_a), bool(trans_b), ACT_CODES[act], bool(act_bwd),
                 float(alpha), float(beta), int(out.dtype == torch.float32), s, _p(ws), _stream(), int(_dbg),
-                int(variant))
+                int(variant), _p(bsum))
     STATS["gemmp"] += 1
     return out
 

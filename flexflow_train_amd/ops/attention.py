@@ -565,14 +565,17 @@ class MultiHeadAttentionOp(OpImpl):
         dx_q = dx_k = dx_v = None
         if self_attn:
             d2 = dproj.view(B * Sq, 3 * Hl * kd)
-            if db_in is not None:
-                if gpu:
-                    K.colsum_act(d2, None, "none", db_in.reshape(-1), write_dx=False)
-                else:
-                    acc_grad(db_in, d2.float().sum(0))
+            # on the GPU the bias gradient rides in the weight-gradient GEMM where
+            # that wins (wgrad_matmul bsum); the column-sum pass otherwise
+            bsum = db_in.reshape(-1) if (db_in is not None and gpu) else None
+            if db_in is not None and not gpu:
+                acc_grad(db_in, d2.float().sum(0))
+            if bsum is not None and dW_views is None:
+                K.colsum_act(d2, None, "none", bsum, write_dx=False)
             if dW_views is not None:
                 if gpu:
-                    wgrad_matmul(ctx, x2, d2, dW_views["qkv"], wbeta)
+                    if not wgrad_matmul(ctx, x2, d2, dW_views["qkv"], wbeta, bsum) and bsum is not None:
+                        K.colsum_act(d2, None, "none", bsum, write_dx=False)
                 else:
                     acc_grad(dW_views["qkv"], x2.float().t() @ d2.float())
             if need_input_grad[0]:

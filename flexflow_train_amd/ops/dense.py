@@ -62,6 +62,7 @@ class LinearOp(OpImpl):
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
         x2, pre, W = saved
+        bsum = None
         dy = grad_outputs[0]
         act = ctx.a("activation", "none")
         dy2 = dy.reshape(-1, dy.shape[-1])
@@ -100,7 +101,10 @@ class LinearOp(OpImpl):
                 g = K.colsum_act(dy2, pre, act, db, write_dx=True)
             else:
                 g = dy2
-                if db is not None:
+                # the bias gradient rides in the weight-gradient GEMM below where
+                # that wins (wgrad_matmul bsum); the column-sum pass otherwise
+                bsum = db if (db is not None and dW is not None and dW.is_cuda and g.dtype == torch.bfloat16) else None
+                if db is not None and bsum is None:
                     K.colsum_act(dy2, None, "none", db, write_dx=False)
         else:
             if act != "none":
@@ -114,7 +118,8 @@ class LinearOp(OpImpl):
                 acc_grad(db, g.float().sum(0))
         if dW is not None:
             if dW.is_cuda and g.dtype == torch.bfloat16:
-                wgrad_matmul(ctx, x2, g, dW, ctx.extra.get("wgrad_beta", [1.0])[0])
+                if not wgrad_matmul(ctx, x2, g, dW, ctx.extra.get("wgrad_beta", [1.0])[0], bsum) and bsum is not None:
+                    K.colsum_act(g, None, "none", bsum, write_dx=False)
             elif dW.is_cuda and g.dtype == torch.float32 and x2.dtype == torch.float32 and dW.dtype == torch.float32:
                 matmul(x2, g, trans_a=True, out=dW, beta=ctx.extra.get("wgrad_beta", [1.0])[0])
             else:

@@ -66,6 +66,11 @@ def report() -> str:
         lines.append(f"a{list(ash)} b{list(bsh)} ta={int(ta)} tb={int(tb)} bias={int(bias)} act={act} "
                      f"out={str(odt).replace('torch.', '')} beta={int(beta)} pre={int(pre)} -> {ch}  "
                      + " ".join(f"{k}:{v:.3f}" for k, v in best))
+    for key, sp in _BSUM_CHOICE.items():
+        t = _BSUM_TIMES.get(key, {})
+        lines.append(f"wgrad+bsum a{list(key[0])} b{list(key[1])} out={str(key[2]).replace('torch.', '')} "
+                     f"beta={int(key[3])} -> {'w:%d+bsum' % sp if sp else 'plain+colsum'}  "
+                     + " ".join(f"{k}:{v:.3f}" for k, v in sorted(t.items(), key=lambda kv: kv[1])[:4]))
     return "\n".join(lines)
 
 
@@ -287,6 +292,25 @@ def _lt_candidates(a, b, trans_a, trans_b, bias, act, out, beta, pre):
     return {f"lt:{i}": (lambda i_: (lambda *args: _lt(*args, algo=i_)))(i) for i in range(min(n, _LT_MAX))}
 
 
+def _plain_splits(M: int, N: int, Kd: int):
+    """Split-K degrees offered to the plain-epilogue 256x256-tile kernels:
+    (gemmp's, gemmt's)."""
+    splits, tsplits = {1}, {1}
+    tiles = ((M + 255) // 256) * ((N + 255) // 256)
+    # split-K only where the output tiles leave CUs idle: past two waves of
+    # workgroups a split only adds its fp32 partial slab (GPT-3's logits
+    # GEMM at split 2: 13 GB of partials for nothing)
+    if tiles < 512:
+        # powers of two around the grid-filling degree (gemmp: K-tiles must
+        # split evenly); gemmt also takes uneven splits, so it adds the
+        # degrees that fill one or two waves of workgroups exactly
+        d = K.default_splits(M, N, Kd)
+        pow2 = {s for s in (2, 4, 8, 16, 32) if d / 3 <= s <= 2 * d and s <= max(1, Kd // 512)}
+        splits |= {s for s in pow2 if (Kd // 64) % s == 0}
+        tsplits |= pow2 | {s for s in (round(256 / tiles), round(512 / tiles)) if 2 <= s <= max(1, Kd // 512)}
+    return splits, tsplits
+
+
 def _candidates(a, b, trans_a, trans_b, bias, act, pre, out=None, beta=0.0):
     """name -> callable(a, b, ta, tb, bias, act, out, beta, pre) tried by the autotuner."""
     c = {"hip": _hip} if _LIB_OFF else {"hip": _hip, "blas": _blas}
@@ -310,18 +334,8 @@ def _candidates(a, b, trans_a, trans_b, bias, act, pre, out=None, beta=0.0):
         M, Kd = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
         N = b.shape[0] if trans_b else b.shape[1]
         splits, tsplits = {1}, {1}
-        tiles = ((M + 255) // 256) * ((N + 255) // 256)
-        # split-K only where the output tiles leave CUs idle: past two waves of
-        # workgroups a split only adds its fp32 partial slab (GPT-3's logits
-        # GEMM at split 2: 13 GB of partials for nothing)
-        if bias is None and act == "none" and pre is None and tiles < 512:
-            # powers of two around the grid-filling degree (gemmp: K-tiles must
-            # split evenly); gemmt also takes uneven splits, so it adds the
-            # degrees that fill one or two waves of workgroups exactly
-            d = K.default_splits(M, N, Kd)
-            pow2 = {s for s in (2, 4, 8, 16, 32) if d / 3 <= s <= 2 * d and s <= max(1, Kd // 512)}
-            splits |= {s for s in pow2 if (Kd // 64) % s == 0}
-            tsplits |= pow2 | {s for s in (round(256 / tiles), round(512 / tiles)) if 2 <= s <= max(1, Kd // 512)}
+        if bias is None and act == "none" and pre is None:
+            splits, tsplits = _plain_splits(M, N, Kd)
         if trans_b and not trans_a and bias is None and act == "none" and pre is None \
                 and os.environ.get("FF_GEMMN", "1") != "0":
             c["n:1"] = lambda *args: _gt(*args, splits=1, variant=9)
@@ -540,7 +554,7 @@ def sync_choices() -> int:
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         return 0
     from .dense import _DACT_CHOICE   # fused-vs-plain activation-gradient decisions
-    tables = (_CHOICE, _DACT_CHOICE)
+    tables = (_CHOICE, _DACT_CHOICE, _BSUM_CHOICE)   # _BSUM_CHOICE: fused bias-gradient split counts
     objs: List[Any] = [None] * dist.get_world_size()
     dist.all_gather_object(objs, [dict(t) for t in tables])
     changed = 0
@@ -590,20 +604,92 @@ def _resolve(name: str):
     return lambda *args: _hip256(*args, splits=int(arg))
 
 
-def wgrad_matmul(ctx, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, beta: float):
+# FF_WGRAD_BSUM: 1 (default) = the weight-gradient GEMM also accumulates the
+# bias gradient (gemmp ``bsum``) on the signatures where timing says that beats
+# the GEMM followed by the column-sum pass; 0 = never (A/B runs); 2 = on every
+# eligible signature, unsplit and untimed (tests)
+_BSUM_MODE = os.environ.get("FF_WGRAD_BSUM", "1")
+_BSUM_CHOICE: Dict[Tuple, int] = {}   # signature -> split count of the fused form, 0 = GEMM + column-sum pass
+_BSUM_TIMES: Dict[Tuple, Dict[str, float]] = {}
+
+
+def bsum_key(a, b, out, beta) -> Tuple:
+    return (tuple(a.shape), tuple(b.shape), out.dtype, bool(beta), a.stride(0), b.stride(0), out.stride(0))
+
+
+def _bsum_ok(a, b, out, bsum) -> bool:
+    """What gemmp's ``bsum`` takes: bf16 A^T B on the LDS-DMA gemmt kernel
+    (variant 6, 32-bit operand offsets), fp32 or bf16 output, fp32 sums."""
+    if not (_GT_DMA and _MODE == "auto" and a.is_cuda and bsum.is_cuda and bsum.dtype == torch.float32
+            and bsum.is_contiguous() and bsum.numel() == b.shape[1] and out.dtype in (torch.float32, torch.bfloat16)):
+        return False
+    if not (_hip_ok(a, b, True, False) and K.gemmp_supported(a, b, True, False)):
+        return False
+    if out.stride(1) != 1 or out.stride(0) % 4 or out.data_ptr() % (16 if out.dtype == torch.float32 else 8):
+        return False
+    return a.shape[0] * a.stride(0) * 2 < 1 << 32 and b.shape[0] * b.stride(0) * 2 < 1 << 32
+
+
+def _bsum_splits(a, b, out, beta, bsum) -> int:
+    """Split count at which the weight-gradient GEMM with the fused column
+    sums runs for this signature, 0 for the plain GEMM + column-sum pass.
+    Timed once per signature, outside graph capture (as dense._dact_fused_wins):
+    variant 6 with ``bsum`` at each split count the autotuner offers the shape,
+    against the autotuned plain GEMM followed by ``colsum_act``."""
+    if _BSUM_MODE == "0" or not _bsum_ok(a, b, out, bsum):
+        return 0
+    if _BSUM_MODE == "2":
+        return 1
+    key = bsum_key(a, b, out, beta)
+    hit = _BSUM_CHOICE.get(key)
+    if hit is not None:
+        return hit
+    if torch.cuda.is_current_stream_capturing():
+        return 0
+    scratch = out.clone()
+    db = torch.zeros_like(bsum)
+    matmul(a, b, trans_a=True, out=scratch, beta=beta)   # settles the autotuner's pick first
+    fns: Dict[str, Callable[[], Any]] = {
+        "plain": lambda: (matmul(a, b, trans_a=True, out=scratch, beta=beta),
+                          K.colsum_act(b, None, "none", db, write_dx=False))}
+    for sp in sorted(_plain_splits(a.shape[1], b.shape[1], a.shape[0])[1]):
+        fns[f"w:{sp}"] = (lambda s_: (lambda: K.gemmp(a, b, trans_a=True, out=scratch, beta=beta, splits=s_,
+                                                       variant=6, bsum=db)))(sp)
+    t = _time_all(fns)
+    best = min(t, key=t.get)
+    _BSUM_CHOICE[key] = 0 if best == "plain" else int(best[2:])
+    _BSUM_TIMES[key] = t
+    return _BSUM_CHOICE[key]
+
+
+def wgrad_matmul(ctx, a: torch.Tensor, b: torch.Tensor, out: torch.Tensor, beta: float,
+                 bsum: Optional[torch.Tensor] = None) -> bool:
     """Weight gradient ``out = a^T b (+ beta * out)``.  When the executor
     attached its weight-gradient stream (``ctx.extra["wgrad_stream"]`` =
     (stream, keep-list, storage pointers)), the GEMM is queued there after the
     compute stream's work so far, and runs beside the rest of the backward
-    pass; ``a`` / ``b`` stay referenced until the executor joins the stream."""
+    pass; ``a`` / ``b`` stay referenced until the executor joins the stream.
+
+    ``bsum`` (fp32 [N]): the bias gradient ``+= sum_k b[k, :]`` that goes with
+    this weight gradient.  Returns True when the GEMM accumulated it (the
+    kernel's ``bsum`` epilogue, where ``_bsum_splits`` found it faster than
+    the separate column-sum pass); on False the caller runs that pass.  Never
+    fused on CPU tensors or on the weight-gradient stream (the bias gradient
+    stays on the compute stream)."""
     wg = ctx.extra.get("wgrad_stream")
     if wg is None or not a.is_cuda:
-        return matmul(a, b, trans_a=True, out=out, beta=beta)
+        if bsum is not None and a.is_cuda:
+            sp = _bsum_splits(a, b, out, beta, bsum)
+            if sp:
+                K.gemmp(a, b, trans_a=True, out=out, beta=beta, splits=sp, variant=6, bsum=bsum)
+                return True
+        matmul(a, b, trans_a=True, out=out, beta=beta)
+        return False
     stream, keep, ptrs = wg
     stream.wait_stream(torch.cuda.current_stream(a.device))
     with torch.cuda.stream(stream):
-        r = matmul(a, b, trans_a=True, out=out, beta=beta)
+        matmul(a, b, trans_a=True, out=out, beta=beta)
     for t in (a, b):
         keep.append(t)
         ptrs.add(t.untyped_storage().data_ptr())
-    return r
+    return False
