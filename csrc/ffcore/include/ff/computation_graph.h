@@ -89,6 +89,11 @@ class ComputationGraph {
                                         const std::string& name = "");
   ValueRef layer_norm(ValueRef x, const std::vector<int64_t>& axes, bool affine = true, double eps = 1e-5,
                       const std::string& name = "");
+  // RMS norm over the last axis (gamma only)
+  ValueRef rms_norm(ValueRef x, double eps = 1e-6, bool affine = true, const std::string& name = "");
+  // rotary position embedding of the last dim; positions run along seq_dim (never the last dim)
+  ValueRef rope(ValueRef x, double theta = 10000.0, int64_t seq_dim = -2, bool interleaved = false,
+                const std::string& name = "");
   ValueRef batch_norm(ValueRef x, bool relu = true, const std::string& name = "");
   ValueRef softmax(ValueRef x, int dim = -1, const std::string& name = "");
   ValueRef unary(OpType t, ValueRef x, const std::string& name = "", std::optional<double> scalar = {});

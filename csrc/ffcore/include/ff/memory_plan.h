@@ -69,6 +69,8 @@ struct MemoryPlanConfig {
   //    attention output (flash attention: no score matrix) beside its output;
   //  * SDPA keeps its inputs (q, k, v and the mask, where one is given), its
   //    output and the fp32 LSE; no Sq x Sk buffer;
+  //  * RMS_NORM keeps its input and the fp32 rstd [M], not its output; ROPE
+  //    keeps nothing (its backward is the inverse rotation of the gradient);
   //  * an output that neither its producer's nor any consumer's backward
   //    reads is freed after its last forward reader (the executor drops it
   //    from its environment); otherwise it lives until its last reader's

@@ -152,6 +152,18 @@ ValueRef ComputationGraph::layer_norm(ValueRef x, const std::vector<int64_t>& ax
   return add_layer(a, {x}, name)[0];
 }
 
+ValueRef ComputationGraph::rms_norm(ValueRef x, double eps, bool affine, const std::string& name) {
+  OpAttrs a(OpType::RMS_NORM);
+  a.set("eps", eps).set("elementwise_affine", affine);
+  return add_layer(a, {x}, name)[0];
+}
+
+ValueRef ComputationGraph::rope(ValueRef x, double theta, int64_t seq_dim, bool interleaved, const std::string& name) {
+  OpAttrs a(OpType::ROPE);
+  a.set("theta", theta).set("seq_dim", seq_dim).set("interleaved", interleaved);
+  return add_layer(a, {x}, name)[0];
+}
+
 ValueRef ComputationGraph::batch_norm(ValueRef x, bool relu, const std::string& name) {
   OpAttrs a(OpType::BATCHNORM);
   a.set("relu", relu);

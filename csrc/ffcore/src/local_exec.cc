@@ -1028,6 +1028,8 @@ LocalTrainingBacking::LocalTrainingBacking(const ComputationGraph& cg, LocalOpti
     if (t == OpType::SDPA)
       throw FFError("local execution: scaled-dot-product attention (SDPA node " + node.label.name +
                     ") is not supported");
+    if (t == OpType::RMS_NORM || t == OpType::ROPE)
+      throw FFError("local execution: " + to_string(t) + " (node " + node.label.name + ") is not supported");
     if (!reg.count(t)) throw FFError("local execution: no CPU implementation for " + to_string(t));
     if (t == OpType::MULTIHEAD_ATTENTION && cg_.layer_data_inputs(n).size() != 3)
       throw FFError("local execution: attention key lengths (the fourth input of " + node.label.name +

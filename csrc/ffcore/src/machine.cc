@@ -440,6 +440,7 @@ OpCost CostModel::op_cost_uncached(const OpAttrs& op, const std::vector<Parallel
     }
     int kernels = w.matmul_like ? 2 : 1;
     if (op.type == OpType::MULTIHEAD_ATTENTION) kernels = 4;
+    if (op.type == OpType::RMS_NORM || op.type == OpType::ROPE) kernels = 1;  // one launch each way
     if (op.type == OpType::SDPA) kernels = 1;  // one flash kernel forward, the dQ + dK/dV pair backward
     if (w.flops > 0 || w.bytes > 0) {
       c.forward += kernels * spec_.kernel_launch_overhead;

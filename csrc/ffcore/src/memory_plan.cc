@@ -172,6 +172,10 @@ std::vector<MemoryPlan> plan_memory(const ParallelComputationGraph& pcg, const s
           const double out = static_cast<double>(o.num_elements());
           if (out > 0) own_extra[n] = extra / out;
         }
+      } else if (t == OpType::RMS_NORM) {
+        // the fp32 rstd [M]: two output-sized words per row of N outputs
+        const auto o = node_output_piece(pcg, n);
+        if (!o.dims.empty() && o.dims.back() > 0) own_extra[n] = 2.0 / static_cast<double>(o.dims.back());
       } else if (t == OpType::SDPA) {
         // q, k, v, o and the mask are graph values (kept by the default
         // rules below); on top of them only the fp32 LSE [B, H, Sq], two
@@ -210,6 +214,8 @@ std::vector<MemoryPlan> plan_memory(const ParallelComputationGraph& pcg, const s
       case OpType::EW_DIV:
       case OpType::MULTIHEAD_ATTENTION:
       case OpType::LAYERNORM:
+      case OpType::RMS_NORM:  // backward reads the input (or the emitted sum) and an fp32 [M]
+      case OpType::ROPE:      // backward is the inverse rotation of dy: nothing is kept
       case OpType::POOL2D:
       case OpType::EMBEDDING:
       case OpType::CONCAT:
@@ -241,6 +247,7 @@ std::vector<MemoryPlan> plan_memory(const ParallelComputationGraph& pcg, const s
       case OpType::FLAT:
       case OpType::TRANSPOSE:
       case OpType::REVERSE:
+      case OpType::ROPE:
       case OpType::SOFTMAX:
       case OpType::RELU:
       case OpType::SIGMOID:

@@ -506,6 +506,80 @@ OpSpec layernorm_spec() {
   return s;
 }
 
+// RMS norm over the last axis: y = x * rsqrt(mean(x^2) + eps) * gamma.  Follows
+// layernorm_spec: no partial-sum input, the normalised axis unpartitioned,
+// gamma replicated over every other degree.
+OpSpec rms_norm_spec() {
+  OpSpec s;
+  s.num_inputs = 1;
+  s.defaults = {{"eps", 1e-6}, {"elementwise_affine", true}};
+  s.weights = [](const OpAttrs& a) {
+    return a.b("elementwise_affine") ? std::vector<std::string>{"gamma"} : std::vector<std::string>{};
+  };
+  s.out = [](const OpAttrs& a, const Shapes& in) {
+    require(nd(in.at(0)) >= 1, a, "needs an input of rank >= 1");
+    require(a.f("eps") >= 0.0, a, "eps must not be negative");
+    return Shapes{in.at(0)};
+  };
+  s.wts = [](const OpAttrs& a, const Shapes& in) {
+    if (!a.b("elementwise_affine")) return Shapes{};
+    return Shapes{TensorShape{{in.at(0).dims.back()}, in.at(0).dtype}};
+  };
+  s.pout = [](const OpAttrs& a, const PShapes& in) {
+    auto const& x = in.at(0);
+    require(x.sum_degree == 1, a, "normalizing a partial-sum tensor");
+    require(x.shard_dims.back().degree == 1, a, "normalized axis must be unpartitioned");
+    return PShapes{x};
+  };
+  s.pwts = [](const OpAttrs& a, const PShapes& in) {
+    if (!a.b("elementwise_affine")) return PShapes{};
+    auto const& x = in.at(0);
+    int other = 1;
+    for (int d = 0; d + 1 < x.num_dims(); ++d) other *= x.shard_dims[d].degree;
+    TensorShape w{{x.shard_dims.back().size}, x.dtype};
+    return PShapes{lift_to_parallel_with_degrees(w, 1, other * x.discard_copy_degree, {1})};
+  };
+  return s;
+}
+
+// Rotary position embedding: rotates the pairs of the last dim D by the angle
+// position * theta^(-2i / D); the position is the index along seq_dim.  No
+// weights.  Any degree passes through except on the last dim and on seq_dim.
+OpSpec rope_spec() {
+  OpSpec s;
+  s.num_inputs = 1;
+  s.defaults = {{"theta", 10000.0}, {"seq_dim", int64_t(-2)}, {"interleaved", false}};
+  s.weights = no_weights;
+  s.out = [](const OpAttrs& a, const Shapes& in) {
+    auto const& x = in.at(0);
+    const int n = nd(x);
+    require(n >= 2, a, "needs an input of rank >= 2");
+    const int64_t sd = a.i("seq_dim") < 0 ? a.i("seq_dim") + n : a.i("seq_dim");
+    require(sd >= 0 && sd < n, a, "seq_dim out of range");
+    require(sd != n - 1, a, "seq_dim cannot be the last dim (the rotary dim)");
+    require(x.dims.back() % 2 == 0, a, "the rotary dim (the last dim) must be even");
+    require(a.f("theta") > 0.0, a, "theta must be positive");
+    return Shapes{x};
+  };
+  s.wts = no_weight_shapes;
+  s.pout = [](const OpAttrs& a, const PShapes& in) {
+    auto const& x = in.at(0);
+    const int n = x.num_dims();
+    require(n >= 2, a, "needs an input of rank >= 2");
+    require(x.sum_degree == 1, a, "rotating a partial-sum tensor");
+    const int64_t sd = a.i("seq_dim") < 0 ? a.i("seq_dim") + n : a.i("seq_dim");
+    require(sd >= 0 && sd < n - 1, a, "seq_dim out of range");
+    require(x.shard_dims.back().degree == 1, a, "the rotary dim (the last dim) must be unpartitioned");
+    require(x.shard_dims[sd].degree == 1, a,
+            "the sequence dim must be unpartitioned (a sequence shard needs a position offset; "
+            "sequence-parallel RoPE is out of scope)");
+    registry()[static_cast<int>(OpType::ROPE)].out(a, Shapes{x.reduced_shape()});
+    return PShapes{x};
+  };
+  s.pwts = no_pweight_shapes;
+  return s;
+}
+
 OpSpec softmax_spec() {
   OpSpec s;
   s.num_inputs = 1;
@@ -1489,6 +1563,8 @@ std::unordered_map<int, OpSpec> build_registry() {
   put(OpType::EMBEDDING, embedding_spec());
   put(OpType::MULTIHEAD_ATTENTION, mha_spec());
   put(OpType::SDPA, sdpa_spec());
+  put(OpType::RMS_NORM, rms_norm_spec());
+  put(OpType::ROPE, rope_spec());
   put(OpType::BATCHMATMUL, batch_matmul_spec());
   put(OpType::MATMUL, batch_matmul_spec());
   put(OpType::CONCAT, concat_spec());
@@ -1675,9 +1751,15 @@ OpWork estimate_op_work(const OpAttrs& a, const std::vector<TensorShape>& in,
       r.bytes = static_cast<double>(in[0].size_bytes()) + 2 * static_cast<double>(out[0].size_bytes());
       break;
     case OpType::LAYERNORM:
+    case OpType::RMS_NORM:
     case OpType::BATCHNORM:
     case OpType::SOFTMAX:
       r.flops = 8 * n_out;
+      break;
+    case OpType::ROPE:
+      // two multiplies and an add per element; one read and one write
+      r.flops = 3 * n_out;
+      r.bytes = static_cast<double>(in[0].size_bytes()) + static_cast<double>(out[0].size_bytes());
       break;
     case OpType::POOL2D:
       r.flops = n_out * static_cast<double>(a.i("kernel_h") * a.i("kernel_w"));

@@ -749,6 +749,8 @@ std::string unsupported(const ComputationGraph& cg, int n) {
       if (ax[i] != nd - static_cast<int>(ax.size()) + static_cast<int>(i)) return "layer norm over non-trailing axes";
     return "";
   }
+  if (t == OpType::RMS_NORM) return "RMS norm (RMS_NORM node " + node.label.name + ")";
+  if (t == OpType::ROPE) return "rotary position embedding (ROPE node " + node.label.name + ")";
   if (t == OpType::SDPA) return "scaled-dot-product attention (SDPA node " + node.label.name + ")";
   if (t == OpType::MULTIHEAD_ATTENTION) {
     const auto ins = cg.layer_data_inputs(n);

@@ -70,6 +70,19 @@ PYBIND11_MODULE(_ffkernels, m) {
   }, py::arg("dt"), py::arg("dy"), py::arg("s"), py::arg("mean"), py::arg("rstd"), py::arg("g"), py::arg("dx"),
         py::arg("dg"), py::arg("db"), py::arg("ws"), py::arg("M"), py::arg("N"), py::arg("st"), py::arg("dres") = 0,
         py::arg("dsum") = 0);
+  m.def("rmsnorm_fwd", [](int dt, uintptr_t x, uintptr_t res, uintptr_t sum_out, uintptr_t g, uintptr_t y,
+                          uintptr_t rstd, int M, int N, float eps, uintptr_t st) {
+    rmsnorm_fwd(dt, P(x), P(res), P(sum_out), P(g), P(y), F(rstd), M, N, eps, S(st));
+  });
+  m.def("rmsnorm_bwd_grid", &rmsnorm_bwd_grid);
+  m.def("rmsnorm_bwd", [](int dt, uintptr_t dy, uintptr_t s, uintptr_t rstd, uintptr_t g, uintptr_t dx, uintptr_t dg,
+                          uintptr_t ws, int M, int N, uintptr_t dres, uintptr_t st) {
+    rmsnorm_bwd(dt, P(dy), P(s), F(rstd), P(g), P(dx), F(dg), F(ws), M, N, P(dres), S(st));
+  });
+  m.def("rope", [](int dt, uintptr_t x, uintptr_t y, uintptr_t table, int64_t rows, int S_, int inner, int D,
+                   bool interleaved, bool inverse, uintptr_t st) {
+    rope(dt, P(x), P(y), F(table), rows, S_, inner, D, interleaved, inverse, S(st));
+  });
   m.def("bias_act_fwd", [](int dt, uintptr_t x, uintptr_t bias, uintptr_t pre, uintptr_t y, int64_t M, int64_t N,
                            int op, float alpha, uintptr_t st) {
     bias_act_fwd(dt, P(x), P(bias), P(pre), P(y), M, N, op, alpha, S(st));

@@ -21,6 +21,23 @@ void layernorm_bwd(int dtype, const void* dy, const void* s, const float* mean, 
                    hipStream_t st, const void* dres = nullptr,
                    float* dsum = nullptr);
 
+// ---- rmsnorm.hip
+// y = s * rstd * gamma with s = x (+ res), rstd = rsqrt(mean(s^2) + eps) [M] fp32; N % 8 == 0.  sum_out
+// (optional, only with res) receives s rounded once; the statistics use the unrounded sum.
+void rmsnorm_fwd(int dtype, const void* x, const void* res, void* sum_out, const void* gamma, void* y, float* rstd,
+                 int M, int N, float eps, hipStream_t st);
+// ws: rmsnorm_bwd_grid(M, N) * N floats (block partials of dgamma), needed only with dgamma.
+// dx = rstd * (g - xhat * mean(g * xhat)) [+ dres]; dgamma += colsum(dy * xhat), added in a fixed
+// order (bit-reproducible, no atomics).
+int rmsnorm_bwd_grid(int M, int N);
+void rmsnorm_bwd(int dtype, const void* dy, const void* s, const float* rstd, const void* gamma, void* dx,
+                 float* dgamma, float* ws, int M, int N, const void* dres, hipStream_t st);
+// Rotary embedding of x viewed as [rows, D] into y (y may be x): the position of a row is
+// (row / inner) % S, table is fp32 [S, D / 2, 2] = (cos, sin); D % 16 == 0.  interleaved: pairs
+// (2i, 2i + 1) instead of (i, i + D / 2); inverse: the rotation by the negative angle (the backward).
+void rope(int dtype, const void* x, void* y, const float* table, int64_t rows, int S, int inner, int D,
+          bool interleaved, bool inverse, hipStream_t st);
+
 // ---- elementwise.hip  (op: 0 identity, 1 relu, 2 sigmoid, 3 tanh, 4 gelu, 5 elu, 6 exp)
 void bias_act_fwd(int dtype, const void* x, const void* bias, void* pre, void* y, int64_t M, int64_t N, int op,
                   float alpha, hipStream_t st);

@@ -461,6 +461,24 @@ class FFModel:
         return self._add("LAYERNORM", [input], name, axes=list(axes), elementwise_affine=elementwise_affine,
                          eps=float(eps), use_bias=use_bias)
 
+    def rms_norm(self, input, eps=1e-6, elementwise_affine=True, name=None):
+        """RMS norm over the last axis (the ``RMS_NORM`` operator): y = x *
+        rsqrt(mean(x^2) + eps) * gamma, fp32 math; ``gamma`` (ones at the
+        start) is the only weight and is absent with
+        ``elementwise_affine=False``.  bf16 / fp32 on the GPU with a last dim
+        that is a multiple of 8 runs one HIP kernel each way; an EW_ADD that
+        feeds it is fused into that kernel by the executor."""
+        return self._add("RMS_NORM", [input], name, eps=float(eps), elementwise_affine=bool(elementwise_affine))
+
+    def rope(self, input, theta=10000.0, seq_dim=-2, interleaved=False, name=None):
+        """Rotary position embedding of the last dim (the ``ROPE`` operator);
+        the position of an element is its index along ``seq_dim`` (default -2,
+        never the last dim).  Pairs are (i, i + D / 2) (Hugging Face / NeoX)
+        or, with ``interleaved``, (2i, 2i + 1) (Meta / GPT-J); the angle of
+        pair i at position p is p * theta^(-2i / D).  No weights."""
+        return self._add("ROPE", [input], name, theta=float(theta), seq_dim=int(seq_dim),
+                         interleaved=bool(interleaved))
+
     def batch_matmul(self, A, B, a_seq_length_dim=None, b_seq_length_dim=None, name=None):
         return self._add("BATCHMATMUL", [A, B], name,
                          a_seq_length_dim=-1 if a_seq_length_dim is None else a_seq_length_dim,

@@ -104,6 +104,8 @@ class OpType(Enum):
     MIN = 2054
     MULTIHEAD_ATTENTION = 2060
     SDPA = 2061
+    RMS_NORM = 2062
+    ROPE = 2063
     GETITEM = 2070
     GETATTR = 2080
     EXPAND = 2081

@@ -233,6 +233,13 @@ def _rebind_parameter_ops(gm: torch.fx.GraphModule, example_inputs) -> Tuple[tor
             m = nn.LayerNorm(shape, eps=eps, elementwise_affine=w is not None)
             if w is not None:
                 m.weight, m.bias = w, b
+        elif t in (F.rms_norm, torch.rms_norm):
+            x, shape = args[0], args[1]
+            w = param_of(args[2] if len(args) > 2 else node.kwargs.get("weight"))
+            eps = args[3] if len(args) > 3 else node.kwargs.get("eps")
+            m = nn.RMSNorm(shape, eps=eps, elementwise_affine=w is not None)
+            if w is not None:
+                m.weight = w
         elif t in (F.max_pool2d, torch.max_pool2d, F.avg_pool2d, torch._C._nn.avg_pool2d):
             x = args[0]
             ks = args[1] if len(args) > 1 else node.kwargs["kernel_size"]

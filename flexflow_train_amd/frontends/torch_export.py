@@ -307,6 +307,12 @@ class ATenImporter:
             return FFV(unary[t](self._ffv(a0, node).t, name=name))
         if t == aten.gelu.default:
             return FFV(ff.gelu(self._ffv(a0, node).t, name=name))
+        if t == aten.silu.default:
+            # x * sigmoid(x): two operators (a fused SwiGLU kernel is not offered)
+            x = self._ffv(a0, node)
+            return FFV(ff.multiply(x.t, ff.sigmoid(x.t, name=name + "_sigmoid"), name=name), x.shape)
+        if t == aten.rms_norm.default:
+            return self._rms_norm(args, kwargs, node, name)
         if t == aten.neg.default:
             return FFV(ff.scalar_multiply(self._ffv(a0, node).t, -1.0, name=name))
         if t in (aten._softmax.default, aten.softmax.int):
@@ -414,6 +420,26 @@ class ATenImporter:
         for k, t in enumerate(terms[1:]):
             out = ff.add(out, t, name=name if k == len(terms) - 2 else f"{name}_{k}")
         return FFV(out)
+
+    def _rms_norm(self, args, kwargs, node, name):
+        """aten.rms_norm(input, normalized_shape, weight=None, eps=None) -> one
+        RMS_NORM node over the last axis; the parameter is copied as gamma.  A
+        missing eps is torch's default, the machine epsilon of the input dtype."""
+        p = dict(zip(["input", "normalized_shape", "weight", "eps"], args))
+        p.update(kwargs)
+        x = self._ffv(p["input"], node)
+        shape = [int(s) for s in p["normalized_shape"]]
+        if shape != [int(x.shape[-1])]:
+            raise NotImplementedError(f"{name}: rms_norm over {shape}: only the last axis is supported")
+        w, eps = p.get("weight"), p.get("eps")
+        if w is not None and not isinstance(w, Param):
+            raise NotImplementedError(f"{name}: rms_norm with a non-parameter weight")
+        if eps is None:
+            eps = torch.finfo(_TORCH_DT.get(x.t.data_type, torch.float32)).eps
+        y = self.ff.rms_norm(x.t, eps=float(eps), elementwise_affine=w is not None, name=name)
+        if w is not None:
+            self.weights[name] = {"gamma": ("copy", w.tensor)}
+        return FFV(y, x.shape)
 
     def _sdpa_fused(self, p, node, name):
         """The SDPA node of an aten.scaled_dot_product_attention call, or None (see _sdpa)."""

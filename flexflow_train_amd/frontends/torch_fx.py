@@ -179,8 +179,11 @@ class PyTorchModel:
             elif node.op in ("call_function", "call_method"):
                 _function(em, node)
             elif node.op == "get_attr":
-                # a buffer is taken only as the constant mask of scaled_dot_product_attention
-                if not all(u.target is F.scaled_dot_product_attention and _sdpa_args(u).get("attn_mask") is node
+                # a buffer is taken only as the constant mask of scaled_dot_product_attention,
+                # a parameter only as the weight of F.rms_norm
+                if not all((u.target is F.scaled_dot_product_attention and _sdpa_args(u).get("attn_mask") is node)
+                           or (u.target is F.rms_norm and _rms_args(u).get("weight") is node
+                               and _rms_args(u).get("input") is not node)
                            for u in node.users):
                     raise NotImplementedError(f"get_attr {node.target} (module attributes are not supported)")
                 em.const[node.name] = _fetch_attr(self.model, node.target)
@@ -230,6 +233,15 @@ class PyTorchModel:
         elif isinstance(mod, nn.LayerNorm):
             emit("LAYER_NORM", fn=lambda: ff.layer_norm(x, [-1], mod.elementwise_affine, mod.eps, name=name),
                  weights={"gamma": ("copy", mod.weight), "beta": ("copy", mod.bias)} if mod.elementwise_affine else None)
+        elif isinstance(mod, nn.RMSNorm):
+            if len(mod.normalized_shape) != 1:
+                raise NotImplementedError(f"{name}: nn.RMSNorm over {tuple(mod.normalized_shape)}: only the last axis")
+            eps = _rms_eps(mod.eps)
+            emit("RMS_NORM", eps, int(mod.elementwise_affine),
+                 fn=lambda: ff.rms_norm(x, eps, mod.elementwise_affine, name=name),
+                 weights={"gamma": ("copy", mod.weight)} if mod.elementwise_affine else None)
+        elif isinstance(mod, nn.SiLU):
+            _silu(em, name, ins[0], outs)
         elif isinstance(mod, nn.Embedding):
             emit("EMBEDDING", mod.num_embeddings, mod.embedding_dim, AggrMode.AGGR_MODE_NONE.value,
                  fn=lambda: ff.embedding(x, mod.num_embeddings, mod.embedding_dim, AggrMode.AGGR_MODE_NONE, name=name),
@@ -264,6 +276,48 @@ def _unary(ff, op, x, name):
             "ELU": lambda: ff.elu(x, name=name), "IDENTITY": lambda: ff.identity(x, name=name),
             "EXP": lambda: ff.exp(x, name=name), "SIN": lambda: ff.sin(x, name=name),
             "COS": lambda: ff.cos(x, name=name), "RSQRT": lambda: ff.rsqrt(x, name=name)}[op]()
+
+
+def _rms_eps(eps) -> float:
+    """torch's default (eps=None) is the machine epsilon of the input dtype; imported graphs are fp32."""
+    return float(torch.finfo(torch.float32).eps if eps is None else eps)
+
+
+def _silu(em: _Emitter, name, x_name, outs):
+    """SiLU as two operators, multiply(x, sigmoid(x)): lines ``<name>_sigmoid`` and ``<name>``."""
+    sg = name + "_sigmoid"
+    em.line(sg, [x_name], [name], "SIGMOID")
+    em.line(name, [x_name, sg], outs, "MULTIPLY")
+    if em.ff is not None:
+        x = em.out.get(x_name)
+        em.out[sg] = em.ff.sigmoid(x, name=sg)
+        em.out[name] = em.ff.multiply(x, em.out[sg], name=name)
+
+
+_RMS_ARGS = ["input", "normalized_shape", "weight", "eps"]
+
+
+def _rms_args(node) -> dict:
+    p = dict(zip(_RMS_ARGS, node.args))
+    p.update(node.kwargs)
+    return p
+
+
+def _rms_norm_fn(em: _Emitter, node):
+    """F.rms_norm(x, [N], weight, eps) -> one RMS_NORM node; the weight is a parameter fetched by get_attr."""
+    name, p = node.name, _rms_args(node)
+    x, w = p["input"], p.get("weight")
+    if len(list(p["normalized_shape"])) != 1:
+        raise NotImplementedError(f"{name}: rms_norm over {tuple(p['normalized_shape'])}: only the last axis")
+    if w is not None and not (isinstance(w, torch.fx.Node) and w.name in em.const
+                              and isinstance(em.const[w.name], nn.Parameter)):
+        raise NotImplementedError(f"{name}: rms_norm with a weight that is not a module parameter")
+    eps = _rms_eps(p.get("eps"))
+    em.line(name, [x.name], [u.name for u in node.users], "RMS_NORM", eps, int(w is not None))
+    if w is not None:
+        em.weights[name] = {"gamma": ("copy", em.const[w.name])}
+    if em.ff is not None:
+        em.out[name] = em.ff.rms_norm(em.out.get(x.name), eps, w is not None, name=name)
 
 
 def _adaptive_pool(ff, x, out_hw, name):
@@ -374,6 +428,10 @@ def _function(em: _Emitter, node):
 
     if tgt is F.scaled_dot_product_attention:
         _sdpa(em, node)
+    elif tgt is F.rms_norm:
+        _rms_norm_fn(em, node)
+    elif tgt is F.silu or tgt == "silu":
+        _silu(em, name, ins[0], outs)
     elif tgt in _BINARY:
         op = _BINARY[tgt]
         a, b = node.args[0], node.args[1]
@@ -491,6 +549,8 @@ def string_to_ff(lines: Sequence[str], ffmodel, input_tensors: Sequence):
             env[name] = f.batch_norm(x, False, name=name)
         elif op == "LAYER_NORM":
             env[name] = f.layer_norm(x, [-1], name=name)
+        elif op == "RMS_NORM":   # eps; elementwise_affine
+            env[name] = f.rms_norm(x, float(a[0]), bool(int(a[1])), name=name)
         elif op == "EMBEDDING":
             env[name] = f.embedding(x, int(a[0]), int(a[1]), AggrMode(int(a[2])), name=name)
         elif op == "DROPOUT":

@@ -139,6 +139,120 @@ def layernorm_bwd(dy, s, mean, rstd, gamma, dgamma=None, dbeta=None, dres=None, 
     return dx
 
 
+def rmsnorm_fwd(x, gamma, eps, residual=None, save_sum=True):
+    """y = s * rstd * gamma with s = x [+ residual] and rstd = rsqrt(mean(s^2)
+    + eps); returns (y, sum_or_x, rstd).  The statistics come from the
+    unrounded fp32 sum, which is stored rounded once (``save_sum``)."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"rmsnorm: expected bf16 or fp32, got {x.dtype}")
+    _check(x, "x")
+    N = x.shape[-1] if x.dim() else 0
+    if N <= 0 or N % 8:
+        raise ValueError("rmsnorm: last dim must be a positive multiple of 8")
+    M = x.numel() // N
+    if M >= 2 ** 31 - 2 ** 17:
+        raise ValueError("rmsnorm: too many rows")
+    y = torch.empty_like(x)
+    s = None
+    if residual is not None:
+        _check(residual, "residual", x.dtype, x.numel())
+        s = torch.empty_like(x) if save_sum else None
+    if gamma is not None:
+        _check(gamma, "gamma", x.dtype, N)
+    rstd = torch.empty(M, device=x.device, dtype=torch.float32)
+    ext().rmsnorm_fwd(_dt(x), _p(x), _p(residual), _p(s), _p(gamma), _p(y), _p(rstd), M, N, float(eps), _stream())
+    STATS["rmsnorm_fwd"] += 1
+    return y, (s if residual is not None else x), rstd
+
+
+def rmsnorm_bwd(dy, s, rstd, gamma, dgamma=None, dres=None):
+    """dx = rstd * (g - xhat * mean(g * xhat)) [+ dres] with xhat = s * rstd,
+    g = dy * gamma; dgamma (fp32) accumulates colsum(dy * xhat), added in a
+    fixed order: two calls from the same start give the same bits."""
+    if dy.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"rmsnorm: expected bf16 or fp32, got {dy.dtype}")
+    _check(dy, "dy")
+    N = dy.shape[-1] if dy.dim() else 0
+    if N <= 0 or N % 8:
+        raise ValueError("rmsnorm: last dim must be a positive multiple of 8")
+    M = dy.numel() // N
+    if M >= 2 ** 31 - 2 ** 17:
+        raise ValueError("rmsnorm: too many rows")
+    _check(s, "s", dy.dtype, dy.numel())
+    _check(rstd, "rstd", torch.float32, M)
+    if gamma is not None:
+        _check(gamma, "gamma", dy.dtype, N)
+    if dres is not None:
+        _check(dres, "dres", dy.dtype, dy.numel())
+    if dgamma is not None:
+        _check(dgamma, "dgamma", torch.float32, N)
+    dx = torch.empty_like(dy)
+    ws = None
+    if dgamma is not None:
+        ws = torch.empty(ext().rmsnorm_bwd_grid(M, N) * N, device=dy.device, dtype=torch.float32)
+    ext().rmsnorm_bwd(_dt(dy), _p(dy), _p(s), _p(rstd), _p(gamma), _p(dx), _p(dgamma), _p(ws), M, N, _p(dres),
+                      _stream())
+    STATS["rmsnorm_bwd"] += 1
+    return dx
+
+
+_ROPE_TABLES: Dict[tuple, torch.Tensor] = {}
+
+
+def rope_table(S: int, D: int, theta: float, device) -> torch.Tensor:
+    """fp32 [S, D / 2, 2] of (cos, sin)(p * theta^(-2i / D)), computed in fp64
+    on the host and rounded once; built on the first use of (S, D, theta,
+    device) and kept, so a captured step only reads it."""
+    device = torch.device(device)
+    key = (int(S), int(D), float(theta), device.type, device.index)
+    t = _ROPE_TABLES.get(key)
+    if t is None:
+        inv = torch.pow(torch.tensor(float(theta), dtype=torch.float64),
+                        -torch.arange(0, D // 2, dtype=torch.float64) * 2.0 / D)
+        ang = torch.arange(S, dtype=torch.float64)[:, None] * inv[None, :]
+        t = torch.stack([torch.cos(ang), torch.sin(ang)], dim=-1).to(torch.float32).contiguous().to(device)
+        _ROPE_TABLES[key] = t
+    return t
+
+
+def rope(x, theta: float = 10000.0, seq_dim: int = -2, interleaved: bool = False, inverse: bool = False, out=None):
+    """Rotary position embedding of the last dim of ``x`` (D % 16 == 0); the
+    position of an element is its index along ``seq_dim``.  Half-split pairs
+    (i, i + D / 2) by default, ``interleaved`` pairs (2i, 2i + 1).  ``inverse``
+    rotates by the negative angle (the backward of the forward call).
+    ``out`` may be ``x`` itself."""
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"rope: expected bf16 or fp32, got {x.dtype}")
+    if x.dim() < 2:
+        raise ValueError("rope: expected a tensor of rank >= 2")
+    _check(x, "x")
+    sd = seq_dim % x.dim() if -x.dim() <= seq_dim < x.dim() else None
+    if sd is None or sd == x.dim() - 1:
+        raise ValueError("rope: seq_dim must name a dim other than the last")
+    D = x.shape[-1]
+    if D <= 0 or D % 16:
+        raise ValueError("rope: the rotary dim (last dim) must be a positive multiple of 16")
+    if not theta > 0:
+        raise ValueError("rope: theta must be positive")
+    S = x.shape[sd]
+    inner = int(math.prod(x.shape[sd + 1:-1]))
+    rows = x.numel() // D
+    if out is None:
+        out = torch.empty_like(x)
+    else:
+        _check(out, "out", x.dtype, x.numel())
+        if out.shape != x.shape:
+            raise ValueError("rope: out must have the shape of x")
+    if rows == 0:
+        return out
+    if max(S, inner) >= 2 ** 31:
+        raise ValueError("rope: dims must fit 32 bits")
+    table = rope_table(S, D, theta, x.device)
+    ext().rope(_dt(x), _p(x), _p(out), _p(table), rows, S, inner, D, bool(interleaved), bool(inverse), _stream())
+    STATS["rope"] += 1
+    return out
+
+
 def bias_act_fwd(x, bias, act: str, alpha: float = 1.0, save_pre: bool = True):
     N = x.shape[-1]
     M = x.numel() // N

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 from typing import Callable, Dict, Tuple
 
-from . import bert, cnn, moe, recsys, transformer
+from . import bert, cnn, llama, moe, recsys, transformer
 
 LOSS_CE = "sparse_categorical_crossentropy"
 LOSS_MSE = "mean_squared_error"
@@ -29,6 +29,7 @@ MODELS: Dict[str, Tuple] = {
     "transformer": (transformer.TransformerConfig, transformer.build_transformer, transformer.transformer_synthetic,
                     LOSS_MSE),
     "gpt": (transformer.GPTConfig, transformer.build_gpt, transformer.gpt_synthetic, LOSS_CE),
+    "llama": (llama.LlamaConfig, llama.build_llama, llama.llama_synthetic, LOSS_CE),
     "alexnet": (cnn.CNNConfig, cnn.build_alexnet, None, LOSS_CE),
     "resnet50": (cnn.CNNConfig, cnn.build_resnet50, None, LOSS_CE),
     "resnext50": (cnn.CNNConfig, cnn.build_resnext50, None, LOSS_CE),

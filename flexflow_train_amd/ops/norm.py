@@ -1,4 +1,4 @@
-"""LAYERNORM (optionally fused with the residual add) and BATCHNORM.
+"""LAYERNORM and RMS_NORM (optionally fused with the residual add) and BATCHNORM.
 
 Parity: lib/kernels/src/cuda/ops/layer_norm_kernels.cu, batch_norm_kernels.cu
 (cuDNN training-mode BN with running stats and optional fused ReLU).
@@ -6,6 +6,8 @@ Parity: lib/kernels/src/cuda/ops/layer_norm_kernels.cu, batch_norm_kernels.cu
 ``FUSED_ADD_LAYERNORM`` is produced by the executor's fusion pass from
 EW_ADD -> LAYERNORM (the post-LN transformer block): one HIP kernel reads
 both operands once and writes y, the pre-norm sum and the row statistics.
+``FUSED_ADD_RMS_NORM`` is the same fusion of EW_ADD -> RMS_NORM (the pre-norm
+decoder block, where the sum is also the residual stream: ``emit_sum``).
 """
 from __future__ import annotations
 
@@ -112,6 +114,93 @@ class LayerNormOp(_LayerNormBase):
 
 @register("FUSED_ADD_LAYERNORM")
 class FusedAddLayerNormOp(_LayerNormBase):
+    fused_add = True
+
+
+def _torch_rms_norm(xf, gamma, eps):
+    return torch.nn.functional.rms_norm(xf, (xf.shape[-1],), gamma, eps)
+
+
+class _RMSNormBase(OpImpl):
+    """y = s * rsqrt(mean(s^2) + eps) * gamma over the last axis, s = x (+ the
+    second input when fused with the residual add).  fp32 math, one rounding.
+
+    HIP path (rmsnorm.hip): GPU, N % 8 == 0, bf16 or fp32; saves s (the input
+    itself without a residual) and the fp32 rstd [M].  Everything else runs
+    torch.nn.functional.rms_norm, the same definition."""
+    fused_add = False
+
+    def forward(self, ctx, inputs, weights):
+        x = inputs[0]
+        res = inputs[1] if self.fused_add else None
+        eps = float(ctx.a("eps", 1e-6))
+        gamma = weights[0] if len(weights) > 0 else None
+        N = x.shape[-1]
+        if (x.is_cuda and N > 0 and N % 8 == 0 and x.dtype in (torch.bfloat16, torch.float32)
+                and (res is None or res.dtype == x.dtype) and (gamma is None or gamma.dtype == x.dtype)
+                and K.use_hip(x)):
+            xc = x.contiguous()
+            rc = res.contiguous() if res is not None else None
+            y, s, rstd = K.rmsnorm_fwd(xc.view(-1, N), gamma.reshape(-1) if gamma is not None else None, eps,
+                                       residual=rc.view(-1, N) if rc is not None else None)
+            outs = [y.view(x.shape)]
+            if ctx.extra.get("emit_sum"):
+                outs.append(s.view(x.shape))
+            return outs, ("hip", s, rstd, gamma, N)
+        xs = x + res if res is not None else x
+        with torch.no_grad():
+            y = _torch_rms_norm(xs.float(), gamma.float() if gamma is not None else None, eps).to(x.dtype)
+        outs = [y]
+        if ctx.extra.get("emit_sum"):
+            outs.append(xs)
+        return outs, ("torch", xs, gamma, eps)
+
+    def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
+        dy = grad_outputs[0]
+        dsum_in = grad_outputs[1] if len(grad_outputs) > 1 else None   # other consumers of the sum
+        dg = weight_grads[0] if len(weight_grads) > 0 else None
+        if saved[0] == "hip":
+            _, s, rstd, gamma, N = saved
+            dres = None
+            if dsum_in is not None:
+                dres = dsum_in.contiguous().view(-1, N)
+                if dres.dtype != s.dtype:
+                    dres = dres.to(s.dtype)
+            dyc = dy.contiguous().view(-1, N)
+            if dyc.dtype != s.dtype:
+                dyc = dyc.to(s.dtype)
+            dgk = dg.reshape(-1) if dg is not None and dg.dtype == torch.float32 and dg.is_contiguous() else None
+            tmp = None
+            if dg is not None and dgk is None:
+                tmp = dgk = torch.zeros(N, device=dy.device, dtype=torch.float32)
+            dx = K.rmsnorm_bwd(dyc, s, rstd, gamma.reshape(-1) if gamma is not None else None, dgk,
+                               dres=dres).view(dy.shape)
+            if tmp is not None:
+                acc_grad(dg, tmp.view(dg.shape))
+        else:
+            _, xs, gamma, eps = saved
+            xf = xs.detach().float().requires_grad_(True)
+            gf = gamma.detach().float().requires_grad_(dg is not None) if gamma is not None else None
+            with torch.enable_grad():
+                y = _torch_rms_norm(xf, gf, eps)
+            y.backward(dy.float())
+            dx = xf.grad.to(dy.dtype)
+            if dsum_in is not None:
+                dx = dx + dsum_in.to(dx.dtype)
+            if dg is not None:
+                acc_grad(dg, gf.grad)
+        if self.fused_add:
+            return [dx, dx]
+        return [dx]
+
+
+@register("RMS_NORM")
+class RMSNormOp(_RMSNormBase):
+    fused_add = False
+
+
+@register("FUSED_ADD_RMS_NORM")
+class FusedAddRMSNormOp(_RMSNormBase):
     fused_add = True
 
 

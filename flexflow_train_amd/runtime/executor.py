@@ -502,7 +502,10 @@ class Executor:
             for v in s.inputs:
                 uses.setdefault(v, []).append(s)
         for s in self.steps:
-            if s.kind == "compute" and s.op_type == "LAYERNORM" and len(s.inputs) == 1:
+            if s.kind == "compute" and s.op_type in ("LAYERNORM", "RMS_NORM") and len(s.inputs) == 1:
+                # EW_ADD -> RMS_NORM fuses the same way (FUSED_ADD_RMS_NORM); a
+                # pre-norm decoder is the emit_sum case throughout
+                fused_type = "FUSED_ADD_LAYERNORM" if s.op_type == "LAYERNORM" else "FUSED_ADD_RMS_NORM"
                 v = s.inputs[0]
                 prod = by_out.get(v)
                 if (prod is not None and prod.kind == "compute" and prod.op_type == "EW_ADD" and id(prod) not in moves
@@ -511,8 +514,8 @@ class Executor:
                         and self.value_layout[v] == self.value_layout[prod.inputs[0]]
                         and tuple(self.value_layout[v].piece_shape)
                         == tuple(self.value_layout[prod.inputs[0]].piece_shape)):
-                    s.op_type = "FUSED_ADD_LAYERNORM"
-                    s.ctx.op_type = "FUSED_ADD_LAYERNORM"
+                    s.op_type = fused_type
+                    s.ctx.op_type = fused_type
                     s.inputs = list(prod.inputs)
                     if len(uses.get(v, [])) > 1:
                         # pre-LN residual stream: the sum also feeds the next

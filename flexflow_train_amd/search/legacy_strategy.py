@@ -44,7 +44,8 @@ _TYPE_NAMES = {
     "batch_matmul": "BATCHMATMUL", "batchmatmul": "BATCHMATMUL", "transpose": "TRANSPOSE", "conv2d": "CONV2D",
     "conv": "CONV2D", "pool2d": "POOL2D", "pool": "POOL2D", "softmax": "SOFTMAX", "attention": "MULTIHEAD_ATTENTION",
     "multihead_attention": "MULTIHEAD_ATTENTION", "sdpa": "SDPA", "scaled_dot_product_attention": "SDPA",
-    "layer_norm": "LAYERNORM", "layernorm": "LAYERNORM",
+    "layer_norm": "LAYERNORM", "layernorm": "LAYERNORM", "rms_norm": "RMS_NORM", "rmsnorm": "RMS_NORM",
+    "rope": "ROPE", "rotary_embedding": "ROPE",
     "batch_norm": "BATCHNORM", "flat": "FLAT", "reshape": "RESHAPE", "dropout": "DROPOUT",
 }
 _LOSS_NAMES = ("mse_loss", "loss", "cross_entropy", "sparse_cross_entropy")
