@@ -304,6 +304,18 @@ def _fuse_matmul_add(nodes: List[Node], consts, shapes) -> List[Node]:
     return out
 
 
+def _refuse_window_attrs(op, name, a, p):
+    """Conv / MaxPool / AveragePool attributes the CONV2D and POOL2D operators
+    cannot express: dilation, implicit (auto_pad) padding, end pads that
+    differ from the begin pads."""
+    if any(int(d) != 1 for d in a.get("dilations", [])):
+        raise NotImplementedError(f"{name}: {op} with dilations={list(a['dilations'])}")
+    if a.get("auto_pad", "NOTSET") not in ("NOTSET", "VALID"):
+        raise NotImplementedError(f"{name}: {op} with auto_pad={a['auto_pad']!r}: explicit pads only")
+    if len(p) == 4 and (p[0] != p[2] or p[1] != p[3]):
+        raise NotImplementedError(f"{name}: {op} with pads={list(p)}: begin and end pads must be equal")
+
+
 class ONNXModel:
     def __init__(self, model):
         if isinstance(model, (bytes, bytearray)):
@@ -374,6 +386,12 @@ class ONNXModel:
             k = a["kernel_shape"]
             s = a.get("strides", [1, 1])
             p = list(a.get("pads", [0, 0, 0, 0]))
+            _refuse_window_attrs(op, name, a, p)
+            if int(a.get("ceil_mode", 0)):
+                raise NotImplementedError(f"{name}: {op} with ceil_mode=1")
+            if op == "AveragePool" and int(a.get("count_include_pad", 0)) and any(p):
+                raise NotImplementedError(f"{name}: AveragePool with count_include_pad=1 and pads={p}: the POOL2D "
+                                          "average excludes the padding")
             if node.inputs[0] in pads:
                 x = env[pads[node.inputs[0]][0]]
                 pp = pads[node.inputs[0]][1]
@@ -395,6 +413,7 @@ class ONNXModel:
             k = a.get("kernel_shape", wshape[2:])
             s = a.get("strides", [1, 1])
             p = list(a.get("pads", [0, 0, 0, 0]))
+            _refuse_window_attrs(op, name, a, p)
             if node.inputs[0] in pads:
                 x = env[pads[node.inputs[0]][0]]
                 pp = pads[node.inputs[0]][1]
@@ -553,7 +572,8 @@ def export_torch(module, example_inputs, path: Optional[str] = None, export_para
                 emit("Gemm", ins, n, transB=1)
             elif isinstance(m, nn.Conv2d):
                 if m.padding_mode != "zeros" or isinstance(m.padding, str):
-                    raise NotImplementedError("Conv2d: explicit zero padding only")
+                    raise NotImplementedError(f"Conv2d with padding={m.padding!r}, padding_mode={m.padding_mode!r}: "
+                                              "explicit zero padding only")
                 ins = [x, param(f"{n.target}.weight", m.weight)]
                 if m.bias is not None:
                     ins.append(param(f"{n.target}.bias", m.bias))
@@ -572,8 +592,12 @@ def export_torch(module, example_inputs, path: Optional[str] = None, export_para
                 if m.ceil_mode:
                     raise NotImplementedError("pooling with ceil_mode")
                 ph, pw = pair(m.padding)
+                # what changes the result travels as an attribute, so that an importer can refuse it
+                extra = ({"dilations": pair(m.dilation)} if isinstance(m, nn.MaxPool2d)
+                         else {"count_include_pad": int(m.count_include_pad)})
                 emit("MaxPool" if isinstance(m, nn.MaxPool2d) else "AveragePool", [x], n,
-                     kernel_shape=pair(m.kernel_size), strides=pair(m.stride or m.kernel_size), pads=[ph, pw, ph, pw])
+                     kernel_shape=pair(m.kernel_size), strides=pair(m.stride or m.kernel_size), pads=[ph, pw, ph, pw],
+                     **extra)
             elif isinstance(m, nn.AdaptiveAvgPool2d):
                 if pair(m.output_size) != [1, 1]:
                     raise NotImplementedError("AdaptiveAvgPool2d to a size other than 1")

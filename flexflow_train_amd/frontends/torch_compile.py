@@ -219,7 +219,10 @@ def _rebind_parameter_ops(gm: torch.fx.GraphModule, example_inputs) -> Tuple[tor
         elif t in (torch.conv2d, F.conv2d):
             x, w = args[0], param_of(args[1])
             b = param_of(args[2] if len(args) > 2 else node.kwargs.get("bias"))
-            stride, padding, dilation, groups = (list(args[3:7]) + [1, 0, 1, 1][len(args[3:7]):])
+            stride, padding, dilation, groups = (
+                args[3 + i] if len(args) > 3 + i else node.kwargs.get(k, d)
+                for i, (k, d) in enumerate((("stride", 1), ("padding", 0), ("dilation", 1), ("groups", 1))))
+            # the importer refuses what the CONV2D operator cannot express (dilation, padding="same")
             m = nn.Conv2d(w.shape[1] * groups, w.shape[0], tuple(w.shape[2:]), stride=stride, padding=padding,
                           dilation=dilation, groups=groups, bias=b is not None)
             m.weight = w
@@ -245,8 +248,16 @@ def _rebind_parameter_ops(gm: torch.fx.GraphModule, example_inputs) -> Tuple[tor
             ks = args[1] if len(args) > 1 else node.kwargs["kernel_size"]
             st = args[2] if len(args) > 2 else node.kwargs.get("stride", None)
             pd = args[3] if len(args) > 3 else node.kwargs.get("padding", 0)
-            cls = nn.MaxPool2d if t in (F.max_pool2d, torch.max_pool2d) else nn.AvgPool2d
-            m = cls(ks, stride=st or ks, padding=pd)
+            # every remaining argument travels to the module, where the importer
+            # refuses what the POOL2D operator cannot express
+            if t in (F.max_pool2d, torch.max_pool2d):
+                rest = {k: (args[4 + i] if len(args) > 4 + i else node.kwargs.get(k, d)) for i, (k, d) in
+                        enumerate((("dilation", 1), ("ceil_mode", False), ("return_indices", False)))}
+                m = nn.MaxPool2d(ks, stride=st or ks, padding=pd, **rest)
+            else:
+                rest = {k: (args[4 + i] if len(args) > 4 + i else node.kwargs.get(k, d)) for i, (k, d) in
+                        enumerate((("ceil_mode", False), ("count_include_pad", True), ("divisor_override", None)))}
+                m = nn.AvgPool2d(ks, stride=st or ks, padding=pd, **rest)
         elif t in (F.embedding, torch.embedding):
             x, w = (args[0], param_of(args[1])) if t is F.embedding else (args[1], param_of(args[0]))
             m = nn.Embedding(w.shape[0], w.shape[1])

@@ -11,7 +11,10 @@ Parity: python/flexflow/torch/model.py — ``PyTorchModel(model, ...)``,
 reference's op names and argument orders for the shared ops (LINEAR:
 out_features, acti, bias; CONV2D: out, kh, kw, sh, sw, ph, pw, acti, groups,
 bias; POOL2D: kernel, stride, padding, pool_type, acti; ...) and enum
-integers from core.types.
+integers from core.types.  One extension: a POOL2D whose window, stride or
+padding differs in h and w writes the h values in the reference's three
+fields and appends ``kernel_w; stride_w; padding_w`` after acti (a square
+pool keeps the reference's five-field line).
 
 Design: fx nodes are lowered through a table of small converters that each
 emit one FFModel call *and* one IR line, so the in-memory path and the file
@@ -209,21 +212,20 @@ class PyTorchModel:
                  weights={"kernel": ("linear_t", mod.weight), **({"bias": ("copy", mod.bias)} if mod.bias is not None
                                                                   else {})})
         elif isinstance(mod, nn.Conv2d):
-            kh, kw = mod.kernel_size
-            sh, sw = mod.stride
-            ph, pw = mod.padding
+            kh, kw, sh, sw, ph, pw = _conv_geometry(mod, name)
             emit("CONV2D", mod.out_channels, kh, kw, sh, sw, ph, pw, _acti_int(), mod.groups, int(mod.bias is not None),
                  fn=lambda: ff.conv2d(x, mod.out_channels, kh, kw, sh, sw, ph, pw, ActiMode.AC_MODE_NONE, mod.groups,
                                       mod.bias is not None, name=name),
                  weights={"kernel": ("copy", mod.weight), **({"bias": ("copy", mod.bias)} if mod.bias is not None
                                                               else {})})
         elif isinstance(mod, (nn.MaxPool2d, nn.AvgPool2d)):
-            k = mod.kernel_size if isinstance(mod.kernel_size, int) else mod.kernel_size[0]
-            s = mod.stride if isinstance(mod.stride, int) else mod.stride[0]
-            p = mod.padding if isinstance(mod.padding, int) else mod.padding[0]
+            (kh, kw), (sh, sw), (ph, pw) = _pool_geometry(mod, name)
             pt = PoolType.POOL_MAX if isinstance(mod, nn.MaxPool2d) else PoolType.POOL_AVG
-            emit("POOL2D", k, s, p, pt.value, _acti_int(),
-                 fn=lambda: ff.pool2d(x, k, k, s, s, p, p, pt, name=name))
+            # the reference's line holds one k, s, p; a window that differs in h
+            # and w appends its w values
+            square = (kh, sh, ph) == (kw, sw, pw)
+            emit("POOL2D", kh, sh, ph, pt.value, _acti_int(), *(() if square else (kw, sw, pw)),
+                 fn=lambda: ff.pool2d(x, kh, kw, sh, sw, ph, pw, pt, name=name))
         elif isinstance(mod, nn.AdaptiveAvgPool2d):
             out_hw = mod.output_size if isinstance(mod.output_size, int) else mod.output_size[0]
             emit("ADAPTIVE_POOL2D", out_hw, PoolType.POOL_AVG.value, _acti_int(), fn=lambda: _adaptive_pool(ff, x, out_hw, name))
@@ -268,6 +270,47 @@ class PyTorchModel:
                  weights={"weight": ("mha", mod)})
         else:
             raise NotImplementedError(f"module {type(mod).__name__} ({node.target})")
+
+
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+def _conv_geometry(mod: nn.Conv2d, name):
+    """(kh, kw, sh, sw, ph, pw) of an nn.Conv2d the CONV2D operator can
+    express: explicit zero padding, no dilation."""
+    if _pair(mod.dilation) != (1, 1):
+        raise NotImplementedError(f"{name}: nn.Conv2d with dilation={tuple(mod.dilation)}: the CONV2D operator has no "
+                                  "dilation")
+    if isinstance(mod.padding, str):
+        raise NotImplementedError(f"{name}: nn.Conv2d with padding={mod.padding!r}: explicit padding only")
+    if mod.padding_mode != "zeros":
+        raise NotImplementedError(f"{name}: nn.Conv2d with padding_mode={mod.padding_mode!r}: zero padding only")
+    return (*_pair(mod.kernel_size), *_pair(mod.stride), *_pair(mod.padding))
+
+
+def _pool_geometry(mod, name):
+    """((kh, kw), (sh, sw), (ph, pw)) of an nn.MaxPool2d / nn.AvgPool2d the
+    POOL2D operator can express: floor output sizes, no dilation, averages
+    that exclude the padding."""
+    kind = type(mod).__name__
+    if mod.ceil_mode:
+        raise NotImplementedError(f"{name}: {kind} with ceil_mode=True")
+    k = _pair(mod.kernel_size)
+    s = _pair(mod.stride if mod.stride is not None else mod.kernel_size)
+    p = _pair(mod.padding)
+    if isinstance(mod, nn.MaxPool2d):
+        if _pair(mod.dilation) != (1, 1):
+            raise NotImplementedError(f"{name}: {kind} with dilation={mod.dilation}")
+        if mod.return_indices:
+            raise NotImplementedError(f"{name}: {kind} with return_indices=True")
+    else:
+        if mod.count_include_pad and p != (0, 0):
+            raise NotImplementedError(f"{name}: {kind} with count_include_pad=True and padding={p}: the POOL2D "
+                                      "average excludes the padding")
+        if mod.divisor_override is not None:
+            raise NotImplementedError(f"{name}: {kind} with divisor_override={mod.divisor_override}")
+    return k, s, p
 
 
 def _unary(ff, op, x, name):
@@ -542,7 +585,8 @@ def string_to_ff(lines: Sequence[str], ffmodel, input_tensors: Sequence):
                                  ActiMode(int(a[7])), int(a[8]), bool(int(a[9])), name=name)
         elif op == "POOL2D":
             k, s, p = int(a[0]), int(a[1]), int(a[2])
-            env[name] = f.pool2d(x, k, k, s, s, p, p, PoolType(int(a[3])), ActiMode(int(a[4])), name=name)
+            kw, sw, pw = (int(a[5]), int(a[6]), int(a[7])) if len(a) >= 8 else (k, s, p)
+            env[name] = f.pool2d(x, k, kw, s, sw, p, pw, PoolType(int(a[3])), ActiMode(int(a[4])), name=name)
         elif op == "ADAPTIVE_POOL2D":
             env[name] = _adaptive_pool(f, x, int(a[0]), name)
         elif op == "BATCH_NORM":
