@@ -94,6 +94,8 @@ class ComputationGraph {
   // rotary position embedding of the last dim; positions run along seq_dim (never the last dim)
   ValueRef rope(ValueRef x, double theta = 10000.0, int64_t seq_dim = -2, bool interleaved = false,
                 const std::string& name = "");
+  // gated activation silu(gate) * up; equal shapes, no weights
+  ValueRef swiglu(ValueRef gate, ValueRef up, const std::string& name = "");
   ValueRef batch_norm(ValueRef x, bool relu = true, const std::string& name = "");
   ValueRef softmax(ValueRef x, int dim = -1, const std::string& name = "");
   ValueRef unary(OpType t, ValueRef x, const std::string& name = "", std::optional<double> scalar = {});

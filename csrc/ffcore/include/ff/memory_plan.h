@@ -71,6 +71,7 @@ struct MemoryPlanConfig {
   //    output and the fp32 LSE; no Sq x Sk buffer;
   //  * RMS_NORM keeps its input and the fp32 rstd [M], not its output; ROPE
   //    keeps nothing (its backward is the inverse rotation of the gradient);
+  //  * SWIGLU keeps its two inputs (gate, up), not its output;
   //  * an output that neither its producer's nor any consumer's backward
   //    reads is freed after its last forward reader (the executor drops it
   //    from its environment); otherwise it lives until its last reader's

@@ -164,6 +164,10 @@ ValueRef ComputationGraph::rope(ValueRef x, double theta, int64_t seq_dim, bool 
   return add_layer(a, {x}, name)[0];
 }
 
+ValueRef ComputationGraph::swiglu(ValueRef gate, ValueRef up, const std::string& name) {
+  return add_layer(OpAttrs(OpType::SWIGLU), {gate, up}, name)[0];
+}
+
 ValueRef ComputationGraph::batch_norm(ValueRef x, bool relu, const std::string& name) {
   OpAttrs a(OpType::BATCHNORM);
   a.set("relu", relu);

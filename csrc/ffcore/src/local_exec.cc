@@ -1028,7 +1028,7 @@ LocalTrainingBacking::LocalTrainingBacking(const ComputationGraph& cg, LocalOpti
     if (t == OpType::SDPA)
       throw FFError("local execution: scaled-dot-product attention (SDPA node " + node.label.name +
                     ") is not supported");
-    if (t == OpType::RMS_NORM || t == OpType::ROPE)
+    if (t == OpType::RMS_NORM || t == OpType::ROPE || t == OpType::SWIGLU)
       throw FFError("local execution: " + to_string(t) + " (node " + node.label.name + ") is not supported");
     if (!reg.count(t)) throw FFError("local execution: no CPU implementation for " + to_string(t));
     if (t == OpType::MULTIHEAD_ATTENTION && cg_.layer_data_inputs(n).size() != 3)

@@ -216,6 +216,7 @@ std::vector<MemoryPlan> plan_memory(const ParallelComputationGraph& pcg, const s
       case OpType::LAYERNORM:
       case OpType::RMS_NORM:  // backward reads the input (or the emitted sum) and an fp32 [M]
       case OpType::ROPE:      // backward is the inverse rotation of dy: nothing is kept
+      case OpType::SWIGLU:    // backward reads gate and up (the default for a consumer's inputs)
       case OpType::POOL2D:
       case OpType::EMBEDDING:
       case OpType::CONCAT:

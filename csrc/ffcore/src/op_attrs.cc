@@ -580,6 +580,36 @@ OpSpec rope_spec() {
   return s;
 }
 
+// Gated activation y = silu(gate) * up.  Two inputs of equal shape (no
+// broadcasting), no weights; every degree passes through and must agree on
+// both inputs.
+OpSpec swiglu_spec() {
+  OpSpec s;
+  s.num_inputs = 2;
+  s.weights = no_weights;
+  s.out = [](const OpAttrs& a, const Shapes& in) {
+    require(in.at(0).dims == in.at(1).dims, a, "gate and up must have equal shapes (no broadcasting)");
+    require(in.at(0).dtype == in.at(1).dtype, a, "gate and up must have the same data type");
+    return Shapes{in.at(0)};
+  };
+  s.wts = no_weight_shapes;
+  s.pout = [](const OpAttrs& a, const PShapes& in) {
+    auto const& g = in.at(0);
+    auto const& u = in.at(1);
+    require(g.num_dims() == u.num_dims(), a, "gate and up must have equal shapes (no broadcasting)");
+    for (int i = 0; i < g.num_dims(); ++i) {
+      require(g.shard_dims[i].size == u.shard_dims[i].size, a, "gate and up must have equal shapes (no broadcasting)");
+      require(g.shard_dims[i].degree == u.shard_dims[i].degree, a,
+              "operand shard degrees differ on dim " + std::to_string(i));
+    }
+    require(g.sum_degree == 1 && u.sum_degree == 1, a, "gated activation on partial sums");
+    require(g.discard_copy_degree == u.discard_copy_degree, a, "operands have different copy degrees");
+    return PShapes{g};
+  };
+  s.pwts = no_pweight_shapes;
+  return s;
+}
+
 OpSpec softmax_spec() {
   OpSpec s;
   s.num_inputs = 1;
@@ -1565,6 +1595,7 @@ std::unordered_map<int, OpSpec> build_registry() {
   put(OpType::SDPA, sdpa_spec());
   put(OpType::RMS_NORM, rms_norm_spec());
   put(OpType::ROPE, rope_spec());
+  put(OpType::SWIGLU, swiglu_spec());
   put(OpType::BATCHMATMUL, batch_matmul_spec());
   put(OpType::MATMUL, batch_matmul_spec());
   put(OpType::CONCAT, concat_spec());
@@ -1760,6 +1791,11 @@ OpWork estimate_op_work(const OpAttrs& a, const std::vector<TensorShape>& in,
       // two multiplies and an add per element; one read and one write
       r.flops = 3 * n_out;
       r.bytes = static_cast<double>(in[0].size_bytes()) + static_cast<double>(out[0].size_bytes());
+      break;
+    case OpType::SWIGLU:
+      // exp, reciprocal and two multiplies per element; two reads and one write
+      r.flops = 6 * n_out;
+      r.bytes = 2 * static_cast<double>(in[0].size_bytes()) + static_cast<double>(out[0].size_bytes());
       break;
     case OpType::POOL2D:
       r.flops = n_out * static_cast<double>(a.i("kernel_h") * a.i("kernel_w"));

@@ -750,6 +750,7 @@ std::string unsupported(const ComputationGraph& cg, int n) {
     return "";
   }
   if (t == OpType::RMS_NORM) return "RMS norm (RMS_NORM node " + node.label.name + ")";
+  if (t == OpType::SWIGLU) return "gated activation (SWIGLU node " + node.label.name + ")";
   if (t == OpType::ROPE) return "rotary position embedding (ROPE node " + node.label.name + ")";
   if (t == OpType::SDPA) return "scaled-dot-product attention (SDPA node " + node.label.name + ")";
   if (t == OpType::MULTIHEAD_ATTENTION) {

@@ -83,6 +83,18 @@ PYBIND11_MODULE(_ffkernels, m) {
                    bool interleaved, bool inverse, uintptr_t st) {
     rope(dt, P(x), P(y), F(table), rows, S_, inner, D, interleaved, inverse, S(st));
   });
+  m.def("swiglu_fwd", [](int dt, uintptr_t gate, uintptr_t up, uintptr_t y, int64_t M, int64_t N, int64_t ldg,
+                         int64_t ldu, int64_t ldy, uintptr_t st) {
+    swiglu_fwd(dt, P(gate), P(up), P(y), M, N, ldg, ldu, ldy, S(st));
+  });
+  m.def("swiglu_bwd", [](int dt, uintptr_t dy, uintptr_t gate, uintptr_t up, uintptr_t dgate, uintptr_t dup, int64_t M,
+                         int64_t N, int64_t lddy, int64_t ldg, int64_t ldu, int64_t lddg, int64_t lddu, uintptr_t st) {
+    swiglu_bwd(dt, P(dy), P(gate), P(up), P(dgate), P(dup), M, N, lddy, ldg, ldu, lddg, lddu, S(st));
+  });
+  m.def("gemm_swiglu", [](uintptr_t x, uintptr_t wg, uintptr_t wu, uintptr_t gate_out, uintptr_t up_out, uintptr_t y,
+                          int M, int N, int K, int lda, int ldb, int ldg, int ldu, int ldy, uintptr_t st) {
+    gemm_swiglu(P(x), P(wg), P(wu), P(gate_out), P(up_out), P(y), M, N, K, lda, ldb, ldg, ldu, ldy, S(st));
+  });
   m.def("bias_act_fwd", [](int dt, uintptr_t x, uintptr_t bias, uintptr_t pre, uintptr_t y, int64_t M, int64_t N,
                            int op, float alpha, uintptr_t st) {
     bias_act_fwd(dt, P(x), P(bias), P(pre), P(y), M, N, op, alpha, S(st));

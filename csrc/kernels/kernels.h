@@ -38,6 +38,21 @@ void rmsnorm_bwd(int dtype, const void* dy, const void* s, const float* rstd, co
 void rope(int dtype, const void* x, void* y, const float* table, int64_t rows, int S, int inner, int D,
           bool interleaved, bool inverse, hipStream_t st);
 
+// ---- swiglu.hip
+// y = silu(gate) * up over [M, N] (bf16 or fp32, fp32 math), N % 8 == 0; every tensor has its own row
+// stride (a multiple of 8 elements, at least N) and a 16-byte aligned base, so gate / up (dgate / dup)
+// may be the halves of one [M, 2N] buffer.  Anything else throws std::invalid_argument before the launch.
+void swiglu_fwd(int dtype, const void* gate, const void* up, void* y, int64_t M, int64_t N, int64_t ldg, int64_t ldu,
+                int64_t ldy, hipStream_t st);
+// dgate = dy * up * s * (1 + gate * (1 - s)), dup = dy * gate * s with s = sigmoid(gate).
+void swiglu_bwd(int dtype, const void* dy, const void* gate, const void* up, void* dgate, void* dup, int64_t M,
+                int64_t N, int64_t lddy, int64_t ldg, int64_t ldu, int64_t lddg, int64_t lddu, hipStream_t st);
+// One launch: gate_out = x wg, up_out = x wu (both rounded to bf16) and y = silu(x wg) * (x wu) from the
+// fp32 accumulators, rounded once.  bf16; x [M, K] row-major (lda), wg / wu [K, N] row-major (one ldb);
+// any M, N % 8 == 0, K % 8 == 0 (K tails enter as zeros), strides multiples of 8, bases 16-byte aligned.
+void gemm_swiglu(const void* x, const void* wg, const void* wu, void* gate_out, void* up_out, void* y, int M, int N,
+                 int K, int lda, int ldb, int ldg, int ldu, int ldy, hipStream_t st);
+
 // ---- elementwise.hip  (op: 0 identity, 1 relu, 2 sigmoid, 3 tanh, 4 gelu, 5 elu, 6 exp)
 void bias_act_fwd(int dtype, const void* x, const void* bias, void* pre, void* y, int64_t M, int64_t N, int op,
                   float alpha, hipStream_t st);

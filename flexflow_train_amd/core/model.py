@@ -479,6 +479,15 @@ class FFModel:
         return self._add("ROPE", [input], name, theta=float(theta), seq_dim=int(seq_dim),
                          interleaved=bool(interleaved))
 
+    def swiglu(self, gate, up, name=None):
+        """Gated activation (the ``SWIGLU`` operator): y = silu(gate) * up
+        with silu(g) = g * sigmoid(g), fp32 math.  Two inputs of equal shape
+        (no broadcasting), no weights.  bf16 / fp32 on the GPU with a last
+        dim that is a multiple of 8 runs one HIP kernel each way; with
+        ``perform_fusion`` the executor folds two bias-free LINEAR producers
+        that read the same value into one gate / up / SwiGLU step."""
+        return self._add("SWIGLU", [gate, up], name)
+
     def batch_matmul(self, A, B, a_seq_length_dim=None, b_seq_length_dim=None, name=None):
         return self._add("BATCHMATMUL", [A, B], name,
                          a_seq_length_dim=-1 if a_seq_length_dim is None else a_seq_length_dim,

@@ -106,6 +106,7 @@ class OpType(Enum):
     SDPA = 2061
     RMS_NORM = 2062
     ROPE = 2063
+    SWIGLU = 2064
     GETITEM = 2070
     GETATTR = 2080
     EXPAND = 2081

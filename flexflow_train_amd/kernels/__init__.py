@@ -253,6 +253,127 @@ def rope(x, theta: float = 10000.0, seq_dim: int = -2, interleaved: bool = False
     return out
 
 
+def _rows(t: torch.Tensor, name: str, dtype, shape=None) -> int:
+    """Check an [M, N] GPU operand of the SwiGLU kernels -- unit column stride,
+    a row stride that is a multiple of 8 elements and at least N, a 16-byte
+    aligned base: a dense matrix or a column range of one (a half of an
+    [M, 2N] buffer) -- and return its row stride."""
+    if not t.is_cuda:
+        raise ValueError(f"{name}: expected a GPU tensor")
+    if t.dim() != 2:
+        raise ValueError(f"{name}: expected a 2-D tensor")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: expected {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    ld = t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+    if (t.shape[1] > 1 and t.stride(1) != 1) or ld % 8 or ld < t.shape[1]:
+        raise ValueError(f"{name}: rows must be contiguous, with a row stride that is a multiple of 8")
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name}: data pointer must be 16-byte aligned")
+    return ld
+
+
+def _swiglu_dims(gate):
+    if gate.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"swiglu: expected bf16 or fp32, got {gate.dtype}")
+    if gate.dim() != 2 or gate.shape[1] <= 0 or gate.shape[1] % 8:
+        raise ValueError("swiglu: operands are [M, N] with N a positive multiple of 8")
+    return int(gate.shape[0]), int(gate.shape[1])
+
+
+def swiglu_fwd(gate, up, out=None):
+    """y = silu(gate) * up over [M, N] operands (bf16 or fp32, N % 8 == 0,
+    fp32 math).  Each operand may be a column range of a wider buffer
+    (``_rows``), so gate / up can be the halves of one [M, 2N] tensor."""
+    M, N = _swiglu_dims(gate)
+    ldg = _rows(gate, "gate", gate.dtype)
+    ldu = _rows(up, "up", gate.dtype, (M, N))
+    if out is None:
+        out = torch.empty(M, N, device=gate.device, dtype=gate.dtype)
+    ldy = _rows(out, "out", gate.dtype, (M, N))
+    if M:
+        ext().swiglu_fwd(_dt(gate), _p(gate), _p(up), _p(out), M, N, ldg, ldu, ldy, _stream())
+        STATS["swiglu"] += 1
+    return out
+
+
+def swiglu_bwd(dy, gate, up, dgate=None, dup=None):
+    """(dgate, dup) of y = silu(gate) * up: dgate = dy * up * s * (1 + gate *
+    (1 - s)), dup = dy * gate * s, s = sigmoid(gate).  Without outputs given,
+    dgate | dup are the halves of one new [M, 2N] buffer."""
+    M, N = _swiglu_dims(gate)
+    ldg = _rows(gate, "gate", gate.dtype)
+    ldu = _rows(up, "up", gate.dtype, (M, N))
+    lddy = _rows(dy, "dy", gate.dtype, (M, N))
+    if (dgate is None) != (dup is None):
+        raise ValueError("swiglu_bwd: give both dgate and dup, or neither")
+    if dgate is None:
+        both = torch.empty(M, 2 * N, device=gate.device, dtype=gate.dtype)
+        dgate, dup = both[:, :N], both[:, N:]
+    lddg = _rows(dgate, "dgate", gate.dtype, (M, N))
+    lddu = _rows(dup, "dup", gate.dtype, (M, N))
+    if M:
+        ext().swiglu_bwd(_dt(gate), _p(dy), _p(gate), _p(up), _p(dgate), _p(dup), M, N, lddy, ldg, ldu, lddg, lddu,
+                         _stream())
+        STATS["swiglu"] += 1
+    return dgate, dup
+
+
+def gemm_swiglu_supported(x, wg, wu) -> bool:
+    """What ``gemm_swiglu`` takes: bf16 GPU operands x [M, K], wg / wu [K, N]
+    of one row stride, K % 8 == 0 and N % 8 == 0, row strides multiples of 8,
+    16-byte aligned bases."""
+    if not use_hip(x, wg, wu):
+        return False
+    try:
+        _gemm_swiglu_dims(x, wg, wu)
+    except ValueError:
+        return False
+    return True
+
+
+def _gemm_swiglu_dims(x, wg, wu):
+    if x.dim() != 2 or wg.dim() != 2 or wu.dim() != 2:
+        raise ValueError("gemm_swiglu: x [M, K], wg and wu [K, N]")
+    M, Kd = int(x.shape[0]), int(x.shape[1])
+    N = int(wg.shape[1])
+    if wg.shape[0] != Kd or tuple(wu.shape) != tuple(wg.shape):
+        raise ValueError("gemm_swiglu: x [M, K], wg and wu [K, N]")
+    if N <= 0 or Kd <= 0 or N % 8 or Kd % 8:
+        raise ValueError("gemm_swiglu: N and K must be positive multiples of 8")
+    lda = _rows(x, "x", torch.bfloat16)
+    ldb = _rows(wg, "wg", torch.bfloat16)
+    if _rows(wu, "wu", torch.bfloat16) != ldb:
+        raise ValueError("gemm_swiglu: wg and wu must have the same row stride")
+    return M, N, Kd, lda, ldb
+
+
+def gemm_swiglu(x, wg, wu, gate_out=None, up_out=None, y=None):
+    """One launch: gate_out = x @ wg and up_out = x @ wu (rounded to bf16, kept
+    for the backward) and y = silu(x @ wg) * (x @ wu) from the fp32
+    accumulators, rounded once.  Without outputs given, gate_out | up_out are
+    the halves of one new [M, 2N] buffer.  Returns (gate_out, up_out, y)."""
+    M, N, Kd, lda, ldb = _gemm_swiglu_dims(x, wg, wu)
+    if (gate_out is None) != (up_out is None):
+        raise ValueError("gemm_swiglu: give both gate_out and up_out, or neither")
+    if gate_out is None:
+        both = torch.empty(M, 2 * N, device=x.device, dtype=torch.bfloat16)
+        gate_out, up_out = both[:, :N], both[:, N:]
+    if y is None:
+        y = torch.empty(M, N, device=x.device, dtype=torch.bfloat16)
+    ldg = _rows(gate_out, "gate_out", torch.bfloat16, (M, N))
+    ldu = _rows(up_out, "up_out", torch.bfloat16, (M, N))
+    ldy = _rows(y, "y", torch.bfloat16, (M, N))
+    if max(lda, ldb, ldg, ldu, ldy, M) >= 2 ** 31:
+        raise ValueError("gemm_swiglu: dims must fit 32 bits")
+    if M:
+        ext().gemm_swiglu(_p(x), _p(wg), _p(wu), _p(gate_out), _p(up_out), _p(y), M, N, Kd, lda, ldb, ldg, ldu, ldy,
+                          _stream())
+        STATS["gemm_swiglu"] += 1
+    return gate_out, up_out, y
+
+
 def bias_act_fwd(x, bias, act: str, alpha: float = 1.0, save_pre: bool = True):
     N = x.shape[-1]
     M = x.numel() // N

@@ -29,6 +29,9 @@ class LlamaConfig:
     rms_norm_eps: float = 1e-6
     rope_theta: float = 10000.0
     initializer_range: float = 0.02
+    # the MLP's gate as one SWIGLU node (silu(gate) * up) instead of the
+    # multiply(multiply(gate, sigmoid(gate)), up) chain
+    swiglu_op: bool = False
 
     @property
     def head_dim(self) -> int:
@@ -63,8 +66,12 @@ def build_llama(model: FFModel, cfg: LlamaConfig) -> Tuple[Dict[str, object], ob
         h = model.rms_norm(x, cfg.rms_norm_eps, name=f"{p}.post_attn_norm")
         gate = dense(h, cfg.intermediate_size, f"{p}.gate_proj")
         up = dense(h, cfg.intermediate_size, f"{p}.up_proj")
-        act = model.multiply(gate, model.sigmoid(gate, name=f"{p}.gate_sigmoid"), name=f"{p}.gate_silu")
-        h = dense(model.multiply(act, up, name=f"{p}.gate_up"), E, f"{p}.down_proj")
+        if cfg.swiglu_op:
+            gated = model.swiglu(gate, up, name=f"{p}.gate_up")
+        else:
+            act = model.multiply(gate, model.sigmoid(gate, name=f"{p}.gate_sigmoid"), name=f"{p}.gate_silu")
+            gated = model.multiply(act, up, name=f"{p}.gate_up")
+        h = dense(gated, E, f"{p}.down_proj")
         x = model.add(x, h, name=f"{p}.mlp_residual")
     x = model.rms_norm(x, cfg.rms_norm_eps, name="norm")
     logits = dense(x, cfg.vocab_size, "lm_head")

@@ -18,6 +18,7 @@ import torch
 
 from .. import kernels as K
 from .base import OpContext, OpImpl, acc_grad, register
+from .elementwise import swiglu_backward, swiglu_forward
 from .gemm import matmul, wgrad_matmul
 
 _ACT_T = {
@@ -196,6 +197,115 @@ def dact_report() -> str:
     return "\n".join(f"dact g{list(k[0])} W{list(k[1])} act={k[2]} bias={int(k[3])} -> "
                      f"{'fused' if _DACT_CHOICE.get(k) else 'plain'}  fused:{f:.3f} plain:{p:.3f}"
                      for k, (f, p) in _DACT_TIMES.items())
+
+
+@register("FUSED_GATE_UP_SWIGLU")
+class GateUpSwigluOp(OpImpl):
+    """LINEAR(h; Wg), LINEAR(h; Wu) -> SWIGLU as one step (the executor's
+    fusion of a gated MLP's first half): y = silu(h Wg) * (h Wu), no biases.
+
+    bf16 on the GPU: g | u live in one [M, 2I] buffer, written together with y
+    by the dual-weight GEMM (``K.gemm_swiglu``) where that is supported and
+    measured faster (``_swiglu_fused_wins``), else by two autotuned GEMMs into
+    the halves and ``K.swiglu_fwd``.  The backward writes dg | du into one
+    [M, 2I] buffer with ``K.swiglu_bwd``, takes the weight gradients from the
+    strided halves and dh from two NT GEMMs, the second accumulating.
+    Everything else runs the unfused operators' code paths."""
+
+    def forward(self, ctx: OpContext, inputs, weights):
+        x = inputs[0]
+        x2 = x.reshape(-1, x.shape[-1])
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        Wg, Wu = (W if W.dtype == x2.dtype else W.to(x2.dtype) for W in weights)
+        M, I = x2.shape[0], Wg.shape[1]
+        if x2.is_cuda and x2.dtype == torch.bfloat16 and I % 8 == 0 and M > 0 and K.use_hip(x2):
+            gu = torch.empty(M, 2 * I, device=x2.device, dtype=x2.dtype)
+            g, u = gu[:, :I], gu[:, I:]
+            if K.gemm_swiglu_supported(x2, Wg, Wu) and _swiglu_fused_wins(x2, Wg, Wu):
+                y = K.gemm_swiglu(x2, Wg, Wu, g, u)[2]
+            else:
+                matmul(x2, Wg, out=g)
+                matmul(x2, Wu, out=u)
+                y = K.swiglu_fwd(g, u)
+        else:
+            g, u = ((matmul(x2, W) if x2.is_cuda else x2 @ W) for W in (Wg, Wu))
+            y = swiglu_forward(g, u)
+        return [y.reshape(*x.shape[:-1], I)], (x2, g, u, Wg, Wu)
+
+    def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
+        x2, g, u, Wg, Wu = saved
+        dy = grad_outputs[0]
+        I = Wg.shape[1]
+        dy2 = dy.reshape(-1, I)
+        if dy2.dtype != g.dtype or not dy2.is_contiguous():
+            dy2 = dy2.to(g.dtype).contiguous()
+        if dy2.is_cuda and dy2.data_ptr() % 16:
+            dy2 = dy2.clone()   # a view at an offset: the kernels want a 16-byte aligned base
+        if g.is_cuda and g.dtype == torch.bfloat16 and g.stride(0) == 2 * I:
+            dg, du = K.swiglu_bwd(dy2, g, u)   # the halves of one [M, 2I] buffer
+        else:
+            dg, du = swiglu_backward(dy2, g, u)
+        betas = ctx.extra.get("wgrad_beta", [1.0, 1.0])
+        for x_grad, dW, beta in ((dg, weight_grads[0], betas[0]), (du, weight_grads[1], betas[1])):
+            if dW is None:
+                continue
+            if dW.is_cuda and x_grad.dtype == torch.bfloat16:
+                wgrad_matmul(ctx, x2, x_grad, dW, beta)
+            elif dW.is_cuda and x_grad.dtype == torch.float32 and dW.dtype == torch.float32:
+                matmul(x2, x_grad, trans_a=True, out=dW, beta=beta)
+            else:
+                acc_grad(dW, x2.float().t() @ x_grad.float())
+        if not need_input_grad[0]:
+            return [None]
+        if not dg.is_cuda:
+            return [(dg @ Wg.t() + du @ Wu.t()).reshape(*dy.shape[:-1], Wg.shape[0])]
+        acc = ctx.extra.get("grad_acc", [None])[0]
+        if acc is not None and acc.is_cuda and acc.dtype == dg.dtype and acc.is_contiguous():
+            matmul(dg, Wg, trans_b=True, out=acc.view(-1, Wg.shape[0]), beta=1.0)
+            matmul(du, Wu, trans_b=True, out=acc.view(-1, Wg.shape[0]), beta=1.0)
+            return [acc]
+        dx = matmul(dg, Wg, trans_b=True)
+        matmul(du, Wu, trans_b=True, out=dx, beta=1.0)
+        return [dx.reshape(*dy.shape[:-1], Wg.shape[0])]
+
+
+_SWIGLU_CHOICE = {}
+_SWIGLU_TIMES = {}
+
+
+def _swiglu_fused_wins(x2, Wg, Wu) -> bool:
+    """Measure once per shape (outside graph capture, as ``_dact_fused_wins``):
+    the dual-weight GEMM with the gate epilogue against two autotuned GEMMs
+    into the halves of the g | u buffer followed by ``K.swiglu_fwd``.  Under
+    capture without a remembered measurement the unfused pair runs."""
+    key = (tuple(x2.shape), tuple(Wg.shape), x2.stride(0), Wg.stride(0))
+    hit = _SWIGLU_CHOICE.get(key)
+    if hit is not None:
+        return hit
+    if torch.cuda.is_current_stream_capturing():
+        return False
+    from .gemm import _time_all
+    M, I = x2.shape[0], Wg.shape[1]
+    gu = torch.empty(M, 2 * I, device=x2.device, dtype=x2.dtype)
+    g, u = gu[:, :I], gu[:, I:]
+    y = torch.empty(M, I, device=x2.device, dtype=x2.dtype)
+    matmul(x2, Wg, out=g)   # settles the autotuner's picks first
+    matmul(x2, Wu, out=u)
+    t = _time_all({
+        "fused": lambda: K.gemm_swiglu(x2, Wg, Wu, g, u, y),
+        "pair": lambda: (matmul(x2, Wg, out=g), matmul(x2, Wu, out=u), K.swiglu_fwd(g, u, y))})
+    _SWIGLU_CHOICE[key] = t["fused"] < t["pair"]
+    _SWIGLU_TIMES[key] = (t["fused"], t["pair"])
+    return _SWIGLU_CHOICE[key]
+
+
+def swiglu_report() -> str:
+    """One line per gate / up / SwiGLU step shape: the dual-weight GEMM
+    (gemm_swiglu) vs two GEMMs + swiglu_fwd, ms, and which one runs."""
+    return "\n".join(f"swiglu x{list(k[0])} W{list(k[1])} -> "
+                     f"{'gemm_swiglu' if _SWIGLU_CHOICE.get(k) else 'pair'}  gemm_swiglu:{f:.3f} pair:{p:.3f}"
+                     for k, (f, p) in _SWIGLU_TIMES.items())
 
 
 def _bmm(a, b, trans_a=False, trans_b=False):

@@ -238,6 +238,55 @@ class BinaryOp(OpImpl):
         return [ra, rb]
 
 
+def _swiglu_hip(g, u) -> bool:
+    return (g.is_cuda and u.is_cuda and g.dtype == u.dtype and g.dtype in (torch.bfloat16, torch.float32)
+            and g.dim() >= 1 and g.shape[-1] % 8 == 0 and g.numel() > 0 and g.is_contiguous()
+            and u.is_contiguous() and g.data_ptr() % 16 == 0 and u.data_ptr() % 16 == 0 and K.use_hip(g, u))
+
+
+def swiglu_forward(g, u):
+    """y = silu(g) * u: bf16 / fp32 on the GPU with a last dim that is a
+    multiple of 8 on the HIP kernel (swiglu.hip), everything else in torch."""
+    if _swiglu_hip(g, u):
+        N = g.shape[-1]
+        return K.swiglu_fwd(g.view(-1, N), u.view(-1, N)).view(g.shape)
+    with torch.no_grad():
+        return (torch.nn.functional.silu(g.float()) * u.float()).to(g.dtype)
+
+
+def swiglu_backward(dy, g, u):
+    """(dgate, dup) = (dy * u * s * (1 + g * (1 - s)), dy * g * s), s = sigmoid(g),
+    fp32 math; the HIP kernel where ``swiglu_forward`` takes it, else torch."""
+    if dy.dtype != g.dtype:
+        dy = dy.to(g.dtype)
+    if _swiglu_hip(g, u) and dy.is_cuda:
+        N = g.shape[-1]
+        dy2 = dy.reshape(-1, N)
+        if not dy2.is_contiguous() or dy2.data_ptr() % 16:
+            dy2 = dy2.contiguous()
+        dg, du = torch.empty_like(g), torch.empty_like(u)
+        K.swiglu_bwd(dy2, g.view(-1, N), u.view(-1, N), dg.view(-1, N), du.view(-1, N))
+        return dg, du
+    dyf, gf, uf = dy.float(), g.float(), u.float()
+    s = torch.sigmoid(gf)
+    return (dyf * uf * s * (1 + gf * (1 - s))).to(g.dtype), (dyf * gf * s).to(g.dtype)
+
+
+@register("SWIGLU")
+class SwigluOp(OpImpl):
+    """y = silu(gate) * up on two inputs of equal shape, no weights."""
+
+    def forward(self, ctx, inputs, weights):
+        g, u = inputs
+        if g.shape != u.shape:
+            raise ValueError(f"SWIGLU {ctx.name}: gate {tuple(g.shape)} and up {tuple(u.shape)} differ")
+        return [swiglu_forward(g, u)], (g, u)
+
+    def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
+        dg, du = swiglu_backward(grad_outputs[0], *saved)
+        return [dg if need_input_grad[0] else None, du if need_input_grad[1] else None]
+
+
 @register("DROPOUT")
 class DropoutOp(OpImpl):
     def forward(self, ctx, inputs, weights):

@@ -553,8 +553,8 @@ def sync_choices() -> int:
     import torch.distributed as dist
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         return 0
-    from .dense import _DACT_CHOICE   # fused-vs-plain activation-gradient decisions
-    tables = (_CHOICE, _DACT_CHOICE, _BSUM_CHOICE)   # _BSUM_CHOICE: fused bias-gradient split counts
+    from .dense import _DACT_CHOICE, _SWIGLU_CHOICE   # fused-vs-plain activation-gradient / gate-up decisions
+    tables = (_CHOICE, _DACT_CHOICE, _BSUM_CHOICE, _SWIGLU_CHOICE)   # _BSUM_CHOICE: fused bias-gradient split counts
     objs: List[Any] = [None] * dist.get_world_size()
     dist.all_gather_object(objs, [dict(t) for t in tables])
     changed = 0

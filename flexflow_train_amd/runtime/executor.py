@@ -427,6 +427,7 @@ class Executor:
                 self.loss_value = prod_step.inputs[0]
         if self.cfg.fuse_add_layernorm:
             self._fuse_add_layernorm()
+            self._fuse_gate_up_swiglu()
             self._fuse_conv_bn()
             if os.environ.get("FF_FUSE_DACT", "1") != "0":
                 self._fuse_linear_dact()
@@ -538,6 +539,43 @@ class Executor:
                 keep.append(s)
         self.steps = keep
         self._fuse_linear_bias_into_ln()
+
+    def _fuse_gate_up_swiglu(self):
+        """LINEAR(h; Wg), LINEAR(h; Wu) -> SWIGLU (a gated MLP's first half)
+        becomes one FUSED_GATE_UP_SWIGLU step with input h and weights Wg, Wu,
+        placed where the SWIGLU stood: one dual-weight GEMM with the gate in
+        its epilogue where that wins, g | u and dg | du in one buffer each
+        (ops/dense.py GateUpSwigluOp).  Only when both producers read the same
+        value, have no bias, no activation and no partial sums, each output
+        has the SWIGLU as its only reader and is neither the loss nor the
+        output value, and all layouts agree."""
+        by_out = {o: s for s in self.steps for o in s.outputs}
+        uses: Dict[Value, int] = {}
+        for s in self.steps:
+            for v in s.inputs:
+                uses[v] = uses.get(v, 0) + 1
+        lay = self.value_layout
+        drop = set()
+        for s in self.steps:
+            if s.kind != "compute" or s.op_type != "SWIGLU" or len(s.inputs) != 2 or s.inputs[0] == s.inputs[1]:
+                continue
+            prods = [by_out.get(v) for v in s.inputs]
+            if any(p is None or p.kind != "compute" or p.op_type != "LINEAR" or len(p.inputs) != 1
+                   or len(p.weights) != 1 or p.ctx.a("activation", "none") != "none" or p.ctx.sum_degree != 1
+                   or p.active != s.active for p in prods):
+                continue
+            pg, pu = prods
+            if (pg.inputs[0] != pu.inputs[0] or s.ctx.sum_degree != 1
+                    or any(uses.get(v, 0) != 1 or v in (self.loss_value, self.output_value) for v in s.inputs)
+                    or not (lay[s.inputs[0]] == lay[s.inputs[1]] == lay[s.outputs[0]])
+                    or pg.weights[0].layout != pu.weights[0].layout
+                    or tuple(pg.weights[0].layout.piece_shape) != tuple(pu.weights[0].layout.piece_shape)):
+                continue
+            s.op_type = s.ctx.op_type = "FUSED_GATE_UP_SWIGLU"
+            s.inputs = list(pg.inputs)
+            s.weights = [pg.weights[0], pu.weights[0]]
+            drop.update((id(pg), id(pu)))
+        self.steps = [s for s in self.steps if id(s) not in drop]
 
     def _fuse_linear_bias_into_ln(self):
         """LINEAR(+bias, no activation) -> FUSED_ADD_LAYERNORM: the input
@@ -1252,7 +1290,7 @@ class Executor:
                     # (or aliasing this op's output gradient, which its own dW GEMM
                     # reads) is not offered for in-place accumulation: the op
                     # returns a fresh tensor and _acc adds
-                    side = wg_on and s.op_type in ("LINEAR", "MULTIHEAD_ATTENTION")
+                    side = wg_on and s.op_type in ("LINEAR", "MULTIHEAD_ATTENTION", "FUSED_GATE_UP_SWIGLU")
                     busy = {g.untyped_storage().data_ptr() for g in gouts if g is not None} if side else set()
                     s.ctx.extra["grad_acc"] = [
                         a if (nd and a is not None and not self._wg_reads(a)
