@@ -154,7 +154,9 @@ __global__ __launch_bounds__(256) void sum_to_kernel(const float* __restrict__ f
       jj /= keep_shape.size[d];
       base += c * full_st.s[d];
     }
-    float acc = 0.f;
+    // compensated (Kahan): one thread adds up to ~10^5 terms in sequence, and a
+    // plain fp32 running sum drifts by sqrt(n_red) roundings
+    float acc = 0.f, comp = 0.f;
     for (int64_t r = 0; r < n_red; ++r) {
       int64_t off = base, rr = r;
       for (int d = red_shape.nd - 1; d >= 0; --d) {
@@ -162,7 +164,10 @@ __global__ __launch_bounds__(256) void sum_to_kernel(const float* __restrict__ f
         rr /= red_shape.size[d];
         off += c * full_st.s[d];
       }
-      acc += full[off];
+      const float v = full[off] - comp;
+      const float t = acc + v;
+      comp = (t - acc) - v;
+      acc = t;
     }
     if (beta != 0.f) acc += beta * ld<T>(out + j);
     st<T>(out + j, acc);
@@ -245,9 +250,17 @@ __global__ __launch_bounds__(256) void reduce_kernel(const T* __restrict__ x, T*
     const int64_t in = j % inner, o = j / inner;
     const T* p = x + o * red * inner + in;
     float acc = op == 2 ? -INFINITY : (op == 3 ? INFINITY : (op == 4 ? 1.f : 0.f));
+    float comp = 0.f;  // sum / mean are compensated (Kahan), as in sum_to_kernel
     for (int64_t r = 0; r < red; ++r) {
       const float v = ld<T>(p + r * inner);
-      acc = op == 2 ? fmaxf(acc, v) : (op == 3 ? fminf(acc, v) : (op == 4 ? acc * v : acc + v));
+      if (op <= 1) {
+        const float u = v - comp;
+        const float t = acc + u;
+        comp = (t - acc) - u;
+        acc = t;
+      } else {
+        acc = op == 2 ? fmaxf(acc, v) : (op == 3 ? fminf(acc, v) : acc * v);
+      }
     }
     if (op == 1) acc /= static_cast<float>(red);
     st<T>(y + j, acc);
@@ -255,7 +268,18 @@ __global__ __launch_bounds__(256) void reduce_kernel(const T* __restrict__ x, T*
 }
 
 // ------------------------------------------------------------------ top-k
-// one wave per row; values descending (sorted), indices int64
+// one wave per row; values sorted, indices int64.  The order is total over
+// (value, index) pairs: NaN first (torch.topk's rule: NaN is the largest
+// value), then value descending, then index ascending.  Being total and strict
+// it gives every round exactly one pick while k <= n, so every index written
+// lies in [0, n) whatever the row holds.
+__device__ __forceinline__ bool topk_before(float av, int ai, float bv, int bi) {
+  const bool an = av != av, bn = bv != bv;
+  if (an != bn) return an;
+  if (!an && av != bv) return av > bv;
+  return ai < bi;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ x, T* __restrict__ vals,
                                                    int64_t* __restrict__ idx, int64_t rows, int n, int k) {
@@ -263,16 +287,16 @@ __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ x, T* _
   const int64_t row = static_cast<int64_t>(blockIdx.x) * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const T* xr = x + row * n;
-  int last_idx = -1;
-  float last_val = INFINITY;
+  int last_idx = -1;  // -1: no pick yet, every element is a candidate
+  float last_val = 0.f;
   for (int t = 0; t < k; ++t) {
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
+    float best = 0.f;
+    int bi = -1;      // -1: this lane has no candidate
     for (int j = lane; j < n; j += 64) {
       const float v = ld<T>(xr + j);
-      // strictly after the previous pick in (value desc, index asc) order
-      const bool after = v < last_val || (v == last_val && j > last_idx);
-      if (after && (v > best || (v == best && j < bi))) {
+      // strictly after the previous pick in the order above
+      const bool after = last_idx < 0 || topk_before(last_val, last_idx, v, j);
+      if (after && (bi < 0 || topk_before(v, j, best, bi))) {
         best = v;
         bi = j;
       }
@@ -280,13 +304,14 @@ __global__ __launch_bounds__(256) void topk_kernel(const T* __restrict__ x, T* _
     for (int o = 32; o > 0; o >>= 1) {
       const float ov = __shfl_xor(best, o, 64);
       const int oi = __shfl_xor(bi, o, 64);
-      if (ov > best || (ov == best && oi < bi)) {
+      if (oi >= 0 && (bi < 0 || topk_before(ov, oi, best, bi))) {
         best = ov;
         bi = oi;
       }
     }
-    if (lane == 0) {
-      st<T>(vals + row * k + t, best);
+    // k <= n (checked by the launcher) leaves a candidate in every round
+    if (lane == 0 && bi >= 0) {
+      vals[row * k + t] = xr[bi];  // the element itself: NaN payload and the sign of zero survive
       idx[row * k + t] = bi;
     }
     last_val = best;
@@ -307,8 +332,8 @@ __device__ __forceinline__ float un_op(int op, float x, float s) {
     case 5: return __logf(x);
     case 6: return sqrtf(x);
     case 7: return rsqrtf(x);
-    case 8: return __sinf(x);
-    case 9: return __cosf(x);
+    case 8: return sinf(x);
+    case 9: return cosf(x);
     case 10: return x > 0.f ? x : s * x;
     case 11: return ceilf(x);
     case 12: return rintf(x);
@@ -324,8 +349,8 @@ __device__ __forceinline__ float un_grad(int op, float x, float s) {
     case 5: return 1.f / x;
     case 6: return 0.5f * rsqrtf(x);
     case 7: { const float r = rsqrtf(x); return -0.5f * r * r * r; }
-    case 8: return __cosf(x);
-    case 9: return -__sinf(x);
+    case 8: return cosf(x);
+    case 9: return -sinf(x);
     case 10: return x > 0.f ? 1.f : s;
     default: return 0.f;  // ceil / round
   }
@@ -346,29 +371,84 @@ __global__ __launch_bounds__(256) void unary_kernel(const T* __restrict__ x, con
 // squared error 3, absolute error 4: loss += sum (p-y)^2 / C, count += rows,
 // so no element-wise torch kernels run around the loss).  Labels may be fp32
 // or the prediction's dtype.
+//
+// The sums are formed in fp64 and reach each fp32 metric slot in one rounded
+// addition: every block leaves its two partial sums in g_mse_part, and the
+// block that finishes last adds them up and updates the slots.  (One fp32
+// atomic per block and slot left the totals with about sqrt(blocks) roundings
+// at their own size, 3 to 6 ulps at 256 blocks, in an order that changed from
+// run to run.)  The scratch is per device and needs no allocation, so the
+// launch stays capturable; like the shared split-K workspace it requires MSE
+// launches on one device to be stream-ordered.
+constexpr int kMseMaxBlocks = 1024;
+__device__ double g_mse_part[2 * kMseMaxBlocks];
+__device__ unsigned int g_mse_done;
+
+__device__ __forceinline__ double block_sum_f64(double v, double* sm) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+  __syncthreads();
+  v = (sm[0] + sm[1]) + (sm[2] + sm[3]);
+  __syncthreads();
+  return v;
+}
+
+// *slot = round(*slot + v), the sum taken in fp64 and rounded once
+__device__ __forceinline__ void add_rounded_once(float* slot, double v) {
+  unsigned int* u = reinterpret_cast<unsigned int*>(slot);
+  unsigned int old = *u, seen;
+  do {
+    seen = old;
+    const float nv = static_cast<float>(static_cast<double>(__uint_as_float(seen)) + v);
+    old = atomicCAS(u, seen, __float_as_uint(nv));
+  } while (old != seen);
+}
+
 template <typename T, typename L>
 __global__ __launch_bounds__(256) void mse_kernel(const T* __restrict__ p, const L* __restrict__ y,
                                                   T* __restrict__ grad, float* __restrict__ metrics, int64_t n,
                                                   float scale, int full, float inv_c, float rows) {
-  float se = 0.f, ae = 0.f;
+  double se = 0.0, ae = 0.0;
   for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += static_cast<int64_t>(gridDim.x) * 256) {
-    const float d = ld<T>(p + i) - static_cast<float>(y[i]);
-    se += d * d;
-    ae += fabsf(d);
-    if (grad) st<T>(grad + i, scale * d);
+    const double dd = static_cast<double>(ld<T>(p + i)) - static_cast<double>(static_cast<float>(y[i]));
+    se += dd * dd;
+    ae += fabs(dd);
+    if (grad) st<T>(grad + i, scale * static_cast<float>(dd));
   }
-  __shared__ float red[8];
-  se = block_sum<256>(se, red);
-  ae = block_sum<256>(ae, red + 4);
-  if (threadIdx.x == 0 && metrics) {
+  if (!metrics) return;
+  __shared__ double red[4];
+  __shared__ bool last;
+  se = block_sum_f64(se, red);
+  ae = block_sum_f64(ae, red);
+  if (threadIdx.x == 0) {
+    g_mse_part[2 * blockIdx.x] = se;
+    g_mse_part[2 * blockIdx.x + 1] = ae;
+    __threadfence();
+    last = atomicAdd(&g_mse_done, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!last) return;
+  __threadfence();
+  const volatile double* part = g_mse_part;
+  se = 0.0;
+  ae = 0.0;
+  for (int b = threadIdx.x; b < static_cast<int>(gridDim.x); b += 256) {
+    se += part[2 * b];
+    ae += part[2 * b + 1];
+  }
+  se = block_sum_f64(se, red);
+  ae = block_sum_f64(ae, red);
+  if (threadIdx.x == 0) {
+    g_mse_done = 0;  // ready for the next launch
     if (full) {
-      atomicAdd(metrics + 0, se * inv_c);
-      if (blockIdx.x == 0) atomicAdd(metrics + 2, rows);
-      atomicAdd(metrics + 3, se);
-      atomicAdd(metrics + 4, ae);
+      add_rounded_once(metrics + 0, se * static_cast<double>(inv_c));
+      add_rounded_once(metrics + 2, static_cast<double>(rows));
+      add_rounded_once(metrics + 3, se);
+      add_rounded_once(metrics + 4, ae);
     } else {
-      atomicAdd(metrics + 0, se);
-      atomicAdd(metrics + 1, ae);
+      add_rounded_once(metrics + 0, se);
+      add_rounded_once(metrics + 1, ae);
     }
   }
 }
@@ -632,7 +712,7 @@ void mse_loss_full(int dtype, int label_dtype, const void* pred, const void* lab
     using T = decltype(t);
     auto go = [&](auto l) {
       using L = decltype(l);
-      hipLaunchKernelGGL((mse_kernel<T, L>), dim3(std::min(grid1(n), 1024)), dim3(256), 0, st,
+      hipLaunchKernelGGL((mse_kernel<T, L>), dim3(std::min(grid1(n), kMseMaxBlocks)), dim3(256), 0, st,
                          static_cast<const T*>(pred), static_cast<const L*>(label), static_cast<T*>(grad), metrics, n,
                          scale, full, 1.f / static_cast<float>(std::max<int64_t>(cols, 1)), static_cast<float>(rows));
     };
