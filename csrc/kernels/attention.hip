@@ -32,7 +32,8 @@
 //
 // Kernels: attn_fwd_kernel, attn_bwd_dq_kernel and attn_bwd_dkdv_kernel, each
 // for D in {64, 128} x CAUSAL x DROP x VARLEN (and, with VARLEN, PACKED) plus
-// D x DROP with BIAS and D x CAUSAL with GQA, and attn_bwd_onepass_kernel;
+// D x DROP with BIAS and D x CAUSAL with GQA, attn_bwd_onepass_kernel, and
+// attn_bwd_dbias_kernel for D x DROP (the bias gradient, after the BIAS pair);
 // attention_fwd / attention_bwd pick one through with_head and
 // with_features.  Packed calls also launch
 // attn_segment_offsets_kernel (before) and attn_pack_tail_kernel (after).
@@ -138,7 +139,9 @@
 //    everywhere; the dQ kernel takes its lse as +inf and the dK/dV kernel
 //    parks S' = -inf for it, so P = 0 (never exp2(-inf + inf)): dQ = 0, and
 //    the row adds nothing to dK / dV.  dS = P (keep rs dP - delta) and dQ =
-//    scale * dS K are unchanged.  No gradient is produced for the bias.
+//    scale * dS K are unchanged.  The gradient of the bias itself is the
+//    score gradient dS, written by attn_bwd_dbias_kernel when the caller asks
+//    for it (AttnTensors::bias_grad; see the kernel's comment).
 //  * loads: in the forward and dQ kernels a lane owns one query and its
 //    registers hold four consecutive keys per group: one 16-byte load per
 //    group (bias_group).  In the dK/dV kernel a lane owns a key and its
@@ -309,7 +312,8 @@ __device__ __forceinline__ void store_zero_rows(bf16* row, int h) {
 
 // Dropout hash (definition in the header comment).  drop_key is uniform over
 // the workgroup: made a scalar so the per-element xor takes it from an SGPR.
-__device__ __forceinline__ unsigned drop_key(const AttnParams& P, int bh) {
+template <class Params>  // AttnParams, or the bias-gradient kernel's own struct
+__device__ __forceinline__ unsigned drop_key(const Params& P, int bh) {
   uint64_t seed = P.seed;
   if (P.seed_dev) seed += static_cast<uint64_t>(*P.seed_dev);
   return __builtin_amdgcn_readfirstlane(hash_u32(seed, static_cast<uint64_t>(bh)));
@@ -1349,6 +1353,211 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
 }
 
 // ===========================================================================
+// Gradient of the additive score bias (AttnTensors::bias_grad), for learned
+// biases: relative position tables, ALiBi slopes, pair biases.  The bias enters
+// as score = scale * q.k + bias, so its gradient is the score gradient
+//   dS[b, h, q, k] = P (keep rs dP - delta),   P = exp2(t - lse), dP = dO . V
+// with no factor `scale` (that belongs to dQ / dK).  It is written as fp32
+// [Bb, Hb, Sq, Sk], Bb in {1, B} and Hb in {1, H}; an extent of 1 is the sum
+// over that axis (a bias that was broadcast there).  The output's form is the
+// caller's choice and independent of the strides the bias was read with.
+//
+// A kernel of its own with its own parameters (AttnParams and the three
+// kernels above stay what they are), launched after the dQ kernel, whose delta
+// it reads.  Orientation of the dK/dV kernel, because it makes the stores
+// coalesce: 4 waves, a wave owns 32 keys, a lane one key, register r of a
+// 32-query subtile is query acc_row(r) + 4 (lane >> 5), so a register store is
+// 32 lanes x 4 bytes = 128 consecutive bytes of an output row.
+//  * a workgroup owns one OUTPUT tile, 128 keys x 64 queries of element
+//    (bo, ho) of [Bb, Hb], and walks the source (b, h) pairs that reduce into
+//    it as one flat sequence of steps (every b if Bb == 1, times every h if
+//    Hb == 1, b outer), like the (head, tile) steps of the GQA dK/dV kernel.
+//    dS accumulates in 32 fp32 registers over all steps and is stored once
+//    with plain stores: no atomics, no workspace, a fixed summation order (two
+//    calls give equal bits).
+//  * per step the K / V fragments of the wave's keys come straight from global
+//    memory (16-byte loads, one row per lane) into a second register set, and
+//    the step's Q / dO tile with its lse / delta words goes through the
+//    swizzled double-buffered LDS stage, parked as -lse / c and -delta to seed
+//    the accumulators.  All of the next step's loads are issued before this
+//    step's MFMAs; one workgroup-uniform barrier per step.
+//  * per subtile two products, S = Q K^T and dP = dO V^T, then the exp2 /
+//    dropout pass of the dK/dV kernel and acc += dS.  The step's 32 bias words
+//    are requested ahead of the prefetch (vmcnt retires in order: the wait for
+//    them leaves the prefetch in flight).
+//  * a pair under bias = -inf has t = -inf, P = 0, gradient 0; a row whose lse
+//    is -inf is parked as S' = -inf like a row past Sq (never exp2(inf - inf)).
+//  * queries >= Sq and keys >= Sk are never read (zeros take their place) and
+//    never stored, so their register values need no mask.
+//  * D = 64: two waves per SIMD; D = 128: one (the two K / V fragment sets
+//    alone are 128 registers).  No instantiation has scratch
+//    (profiles/attn_bias_grad.txt).
+// Grid: ceil(Sk / 128) x ceil(Sq / 64) x Bb * Hb.  With Bb * Hb small and a
+// short sequence that under-fills the device; a batch split with fixed-order
+// partial sums is not done.
+struct AttnBiasGradParams {
+  TensorView q, k, v, dout;
+  const float* lse;    // [B, H, Sq] log2-domain
+  const float* delta;  // [B, H, Sq], written by the dQ kernel
+  const float* bias;
+  int64_t bias_sb, bias_sh, bias_sq;  // as AttnParams
+  float* out;                         // [Bb, Hb, Sq, Sk], the key axis contiguous
+  int64_t out_sb, out_sh, out_sq;
+  int B, H, Sq, Sk, Bb, Hb;
+  float scale_log2, inv_scale_log2;
+  unsigned drop_thr;
+  float drop_rs;
+  uint64_t seed;
+  const int64_t* seed_dev;
+};
+
+template <int D, bool DROP>
+__global__ __launch_bounds__(256, (D == 64 && !DROP ? 2 : 1)) void attn_bwd_dbias_kernel(AttnBiasGradParams P) {
+  constexpr int KS = D / 16, QT = 64, KW = 32;
+  constexpr int TILE_BYTES = QT * D * 2;
+  constexpr int STAGE = 2 * TILE_BYTES + 2 * QT * 4;  // Q, dO, -lse / c, -delta
+  __shared__ __attribute__((aligned(16))) unsigned char smem[2 * STAGE];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, h = lane >> 5;
+  const int bo = blockIdx.z / P.Hb, ho = blockIdx.z % P.Hb;
+  const int q0 = blockIdx.y * QT;
+  const int key = blockIdx.x * (4 * KW) + wave * KW + (lane & 31);
+  const bool k_ok = key < P.Sk;
+  // the sources of this tile: heads h_lo .. h_hi of every batch from b on,
+  // n_steps of them; (b, hh) is the step's source, uniform over the workgroup
+  const int h_lo = P.Hb == 1 ? 0 : ho, h_hi = P.Hb == 1 ? P.H : ho + 1;
+  const int n_steps = (P.Bb == 1 ? P.B : 1) * (h_hi - h_lo);
+  int b = P.Bb == 1 ? 0 : bo, hh = h_lo;
+
+  // K, V rows of source (sb, sh) as B operands (lane holds row `key`, d = 16ks + 8h ..)
+  auto load_kv = [&](bf16x8 (&kd)[KS], bf16x8 (&vd)[KS], int sb, int sh) {
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      kd[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.k.row(sb, key, sh) + ks * 16 + 8 * h) : bf16x8{};
+      vd[ks] = k_ok ? *reinterpret_cast<const bf16x8*>(P.v.row(sb, key, sh) + ks * 16 + 8 * h) : bf16x8{};
+    }
+  };
+  // raw lse / delta of the tile's rows, shaped at the park point only (see
+  // the dK/dV kernel: arithmetic at the fetch would wait for the load there)
+  float nls = 0.f, nds = 0.f;
+  const bool nok = threadIdx.x < QT && q0 + static_cast<int>(threadIdx.x) < P.Sq;
+  auto fetch_scalars = [&](int sb, int sh) {
+    if (nok) {
+      const int64_t i = (static_cast<int64_t>(sb) * P.H + sh) * P.Sq + q0 + threadIdx.x;
+      nls = P.lse[i];
+      nds = P.delta[i];
+    }
+  };
+  auto park_scalars = [&](unsigned char* stage) {
+    float* ls = reinterpret_cast<float*>(stage + 2 * TILE_BYTES);
+    if (threadIdx.x < QT) {
+      // a row with every key masked (lse = -inf) and a row past Sq: S' = -inf, P = 0
+      ls[threadIdx.x] = (nok && nls > -INFINITY) ? -nls * P.inv_scale_log2 : -INFINITY;
+      ls[QT + threadIdx.x] = nok ? -nds : 0.f;
+    }
+  };
+
+  bf16x8 kf[KS], vf[KS], kn[KS], vn[KS];
+  TileLoader<D, QT> ql, dl;
+  f32x16 acc[2];
+  acc[0] = acc[1] = f32x16{};
+  load_kv(kf, vf, b, hh);
+  ql.load(P.q, b, hh, q0, P.Sq);
+  dl.load(P.dout, b, hh, q0, P.Sq);
+  fetch_scalars(b, hh);
+  ql.store(smem);
+  dl.store(smem + TILE_BYTES);
+  park_scalars(smem);
+  __syncthreads();
+
+  for (int t = 0; t < n_steps; ++t) {
+    unsigned char* stage = smem + (t & 1) * STAGE;
+    const unsigned char* Qt = stage;
+    const unsigned char* Dt = stage + TILE_BYTES;
+    const float* ls = reinterpret_cast<const float*>(stage + 2 * TILE_BYTES);
+    const float* ds = ls + QT;
+    const bool has_next = t + 1 < n_steps;
+    // bias of this step (bb[qt * 16 + r]): the lane's key column of source
+    // (b, hh), 32 lanes reading 128 consecutive bytes of a row; issued ahead
+    // of the next step's loads so that the wait for it leaves them in flight
+    // (the row stride is made opaque per step: as a loop invariant its 32
+    // row offsets were hoisted into 64 scalar registers, which then spilled)
+    int64_t bsq = P.bias_sq;
+    asm volatile("" : "+s"(bsq));
+    const float* bcol = P.bias + b * P.bias_sb + hh * P.bias_sh + static_cast<int64_t>(q0 + 4 * h) * bsq + key;
+    float bb[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) {
+      const int rq = (i >> 4) * 32 + acc_row(i & 15);
+      bb[i] = (k_ok && q0 + rq + 4 * h < P.Sq) ? bcol[static_cast<int64_t>(rq) * bsq] : 0.f;
+    }
+    // the next step's source and all of its loads
+    const bool wrap = hh + 1 == h_hi;
+    const int hh_n = wrap ? h_lo : hh + 1, b_n = wrap ? b + 1 : b;
+    if (has_next) {
+      ql.load(P.q, b_n, hh_n, q0, P.Sq);
+      dl.load(P.dout, b_n, hh_n, q0, P.Sq);
+      fetch_scalars(b_n, hh_n);
+      load_kv(kn, vn, b_n, hh_n);
+    }
+    // dropout: hash index of register r of a subtile = (first query + 4 h +
+    // acc_row(r)) * Sk + key, under the key of the step's source
+    [[maybe_unused]] unsigned dkey = 0, dcol = 0, dsk = static_cast<unsigned>(P.Sk);
+    if constexpr (DROP) {
+      dkey = drop_key(P, b * P.H + hh);
+      dcol = static_cast<unsigned>(q0 + 4 * h) * static_cast<unsigned>(P.Sk) + static_cast<unsigned>(key);
+      asm volatile("" : "+s"(dsk));  // opaque per step, like bsq: 32 more hoisted row offsets otherwise
+    }
+#pragma unroll
+    for (int qt = 0; qt < 2; ++qt) {
+      f32x16 s, dp;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ql_ = qt * 32 + acc_row(r) + 4 * h;
+        s[r] = ls[ql_];
+        dp[r] = DROP ? 0.f : ds[ql_];
+      }
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) {
+        const int off = lds_off<D>(qt * 32 + (lane & 31), 2 * ks + h);
+        const bf16x8 qa = lds_read16(Qt, off), da = lds_read16(Dt, off);
+        s = mfma32(qa, kf[ks], s);
+        dp = mfma32(da, vf[ks], dp);
+      }
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        // P = exp2(c S' + bias log2(e)); a masked pair and a parked row give 0
+        const float pv = fexp2(fmaf(s[r], P.scale_log2, bb[qt * 16 + r] * kLog2e));
+        if constexpr (DROP) {
+          const int rq = qt * 32 + acc_row(r);
+          const bool drop = dropped(dcol + static_cast<unsigned>(rq) * dsk, dkey, P.drop_thr);
+          acc[qt][r] += pv * fmaf(drop ? 0.f : P.drop_rs, dp[r], ds[rq + 4 * h]);
+        } else {
+          acc[qt][r] += pv * dp[r];
+        }
+      }
+    }
+    if (has_next) {
+      unsigned char* nxt = smem + ((t + 1) & 1) * STAGE;
+      ql.store(nxt);
+      dl.store(nxt + TILE_BYTES);
+      park_scalars(nxt);
+#pragma unroll
+      for (int ks = 0; ks < KS; ++ks) kf[ks] = kn[ks], vf[ks] = vn[ks];
+    }
+    __syncthreads();
+    b = b_n, hh = hh_n;
+  }
+
+  // one plain store per register: 32 lanes x 4 bytes of output row qq
+  float* ocol = P.out + bo * P.out_sb + ho * P.out_sh + static_cast<int64_t>(q0 + 4 * h) * P.out_sq + key;
+#pragma unroll
+  for (int i = 0; i < 32; ++i) {
+    const int rq = (i >> 4) * 32 + acc_row(i & 15);
+    if (k_ok && q0 + rq + 4 * h < P.Sq) ocol[static_cast<int64_t>(rq) * P.out_sq] = acc[i >> 4][i & 15];
+  }
+}
+
+// ===========================================================================
 // One-pass backward for D = 64, non-causal, Sk <= 512, no dbias: S, P, dP and
 // dS are formed once per (query, key) tile and feed all three gradients —
 // five MFMA products and one exp2 per pair instead of the seven and two of
@@ -1780,7 +1989,46 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
     if (t.dbq || t.dbk || t.dbv)
       throw std::invalid_argument("attention: grouped-query K / V heads (kv_heads) exclude the fused dbias");
   }
+  if (t.bias_grad.p) {
+    // attn_bwd_dbias_kernel's rules (its parameters are made in attention_bwd)
+    const auto& g = t.bias_grad;
+    if (!t.bias.p) throw std::invalid_argument("attention: bias_grad needs a bias");
+    if (P.G > 1) throw std::invalid_argument("attention: bias_grad excludes grouped-query K / V heads (kv_heads)");
+    if (reinterpret_cast<uintptr_t>(g.p) % 16) throw std::invalid_argument("attention: bias_grad must be 16-byte aligned");
+    if (g.sk != 1) throw std::invalid_argument("attention: the key axis of bias_grad must be contiguous");
+    if (g.sb % 4 || g.sh % 4 || g.sq % 4 || g.sb < 0 || g.sh < 0 || g.sq < 0 || (g.sq == 0 && Sq > 1))
+      throw std::invalid_argument("attention: bias_grad strides must be 0 (summed axis) or positive multiples of 4");
+    if (static_cast<int64_t>(g.sb ? B : 1) * (g.sh ? H : 1) > 65535 || (Sq + 63) / 64 > 65535)
+      throw std::invalid_argument("attention: bias_grad exceeds the grid");
+  }
   return P;
+}
+
+// The bias gradient: one workgroup per 128-key x 64-query tile of [Bb, Hb, Sq, Sk].
+static void launch_bias_grad(const AttnTensors& t, const AttnParams& P, int D, hipStream_t st) {
+  AttnBiasGradParams G{};
+  G.q = P.q; G.k = P.k; G.v = P.v; G.dout = P.dout;
+  G.lse = P.lse;
+  G.delta = P.delta;
+  G.bias = P.bias;
+  G.bias_sb = P.bias_sb; G.bias_sh = P.bias_sh; G.bias_sq = P.bias_sq;
+  G.out = t.bias_grad.p;
+  G.out_sb = t.bias_grad.sb; G.out_sh = t.bias_grad.sh; G.out_sq = t.bias_grad.sq;
+  G.B = P.B; G.H = P.H; G.Sq = P.Sq; G.Sk = P.Sk;
+  G.Bb = t.bias_grad.sb ? P.B : 1;
+  G.Hb = t.bias_grad.sh ? P.H : 1;
+  G.scale_log2 = P.scale_log2;
+  G.inv_scale_log2 = P.inv_scale_log2;
+  G.drop_thr = P.drop_thr; G.drop_rs = P.drop_rs; G.seed = P.seed; G.seed_dev = P.seed_dev;
+  const dim3 grid(static_cast<unsigned>((P.Sk + 127) / 128), static_cast<unsigned>((P.Sq + 63) / 64),
+                  static_cast<unsigned>(G.Bb * G.Hb));
+  auto go = [&](auto d) {
+    constexpr int DD = decltype(d)::value;
+    if (P.drop_thr) hipLaunchKernelGGL((attn_bwd_dbias_kernel<DD, true>), grid, dim3(256), 0, st, G);
+    else hipLaunchKernelGGL((attn_bwd_dbias_kernel<DD, false>), grid, dim3(256), 0, st, G);
+  };
+  if (D == 64) go(std::integral_constant<int, 64>{});
+  else go(std::integral_constant<int, 128>{});  // with_head has refused every other D
 }
 
 // The runtime (D, causal) as compile-time constants: f(integral_constant<int,
@@ -1899,6 +2147,7 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
         if (P.bias) {
           hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, false, DR, false, false, true>), gq, block, 0, st, P);
           hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, false, DR, false, false, true>), gk, block, 0, st, P);
+          if (t.bias_grad.p) launch_bias_grad(t, P, DD, st);  // after the dQ kernel: it reads delta
           return;
         }
       }

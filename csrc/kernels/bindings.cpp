@@ -44,6 +44,17 @@ static void set_bias(AttnTensors& t, const py::tuple& b) {
   t.bias.sq = b[3].cast<int64_t>();
 }
 
+// gradient of the score bias: (ptr, sb, sh, sq, sk) of an fp32 tensor, or an empty tuple
+static void set_bias_grad(AttnTensors& t, const py::tuple& g) {
+  if (g.size() == 0) return;
+  if (g.size() != 5) throw std::invalid_argument("attention bias_grad view must be (ptr, sb, sh, sq, sk)");
+  t.bias_grad.p = reinterpret_cast<float*>(g[0].cast<uintptr_t>());
+  t.bias_grad.sb = g[1].cast<int64_t>();
+  t.bias_grad.sh = g[2].cast<int64_t>();
+  t.bias_grad.sq = g[3].cast<int64_t>();
+  t.bias_grad.sk = g[4].cast<int64_t>();
+}
+
 static void set_dropout(AttnTensors& t, uint32_t drop_t, uint64_t seed, uintptr_t seed_dev) {
   if (!drop_t) return;
   if (drop_t >= (1u << 24)) throw std::invalid_argument("attention: dropout threshold must be below 2^24");
@@ -211,10 +222,11 @@ PYBIND11_MODULE(_ffkernels, m) {
                             int D, float scale, bool causal, uintptr_t st, uintptr_t dbq, uintptr_t dbk,
                             uintptr_t dbv, int64_t db_ld, uintptr_t ws, uint32_t drop_t, uint64_t seed,
                             uintptr_t seed_dev, uintptr_t kv_lens, uintptr_t q_lens, uintptr_t seg_off, int seg_M,
-                            int seg_T, py::tuple bias, int kv_heads) {
+                            int seg_T, py::tuple bias, int kv_heads, py::tuple bias_grad) {
     AttnTensors t;
     t.kv_heads = kv_heads;
     set_bias(t, bias);
+    set_bias_grad(t, bias_grad);
     set_packed(t, seg_off, seg_M, seg_T);
     t.q = tview(q);
     t.k = tview(k);
@@ -239,7 +251,8 @@ PYBIND11_MODULE(_ffkernels, m) {
         py::arg("D"), py::arg("scale"), py::arg("causal"), py::arg("st"), py::arg("dbq") = 0, py::arg("dbk") = 0,
         py::arg("dbv") = 0, py::arg("db_ld") = 0, py::arg("ws") = 0, py::arg("drop_t") = 0, py::arg("seed") = 0,
         py::arg("seed_dev") = 0, py::arg("kv_lens") = 0, py::arg("q_lens") = 0, py::arg("seg_off") = 0,
-        py::arg("seg_M") = 0, py::arg("seg_T") = 0, py::arg("bias") = py::tuple(), py::arg("kv_heads") = 0);
+        py::arg("seg_M") = 0, py::arg("seg_T") = 0, py::arg("bias") = py::tuple(), py::arg("kv_heads") = 0,
+        py::arg("bias_grad") = py::tuple());
   m.def("attention_segment_offsets", [](uintptr_t seg_lens, uintptr_t seg_off, int N, int M, int T, int max_seqlen,
                                         uintptr_t st) {
     attention_segment_offsets(reinterpret_cast<const int32_t*>(seg_lens), reinterpret_cast<int32_t*>(seg_off), N, M,

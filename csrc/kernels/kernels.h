@@ -167,8 +167,8 @@ struct AttnTensors {
   // axis contiguous.  The score of (b, h, q, k) is scale * q.k + bias[b * sb +
   // h * sh + q * sq + k] before the softmax; -inf masks the pair.  A row with
   // every key masked gets o = 0, lse = -inf, dQ = 0.  Masked keys are still
-  // read (unlike with kv_lens): K / V under a mask must be finite.  No
-  // gradient is produced for the bias.  Needs a 16-byte aligned base,
+  // read (unlike with kv_lens): K / V under a mask must be finite.  Its
+  // gradient is bias_grad below.  Needs a 16-byte aligned base,
   // Sk % 4 == 0 and strides that are 0 or multiples of 4; excludes causal,
   // kv_lens, q_lens, seg_offsets and the fused dbias (std::invalid_argument).
   // Always the dQ + dK/dV kernel pair.  p = nullptr: no bias (the kernels of
@@ -178,6 +178,22 @@ struct AttnTensors {
     int64_t sb = 0, sh = 0, sq = 0;
   };
   Bias bias = {};
+  // gradient of the bias (backward only; a learned bias): fp32 [Bb, Hb, Sq,
+  // Sk] with element strides sb / sh / sq / sk.  sb = 0 means Bb = 1, the sum
+  // over the batch; sh = 0 means Hb = 1, the sum over the heads; otherwise
+  // the extent is B / H.  The form is the caller's choice, independent of how
+  // `bias` was broadcast.  Overwritten (not accumulated) by one more launch
+  // after the dQ kernel, attn_bwd_dbias_kernel: the score gradient dS = P
+  // (keep rs dP - delta), 0 under bias = -inf and in a row with every key
+  // masked, summed in a fixed order (two calls give equal bits).  Needs a
+  // bias, kv_heads == H, a 16-byte aligned base, sk == 1 and sb / sh / sq
+  // that are 0 or positive multiples of 4 (std::invalid_argument).  p =
+  // nullptr: no gradient, no launch.
+  struct BiasGrad {
+    float* p = nullptr;
+    int64_t sb = 0, sh = 0, sq = 0, sk = 1;
+  };
+  BiasGrad bias_grad = {};
   // grouped-query attention: the head count of k / v / dk / dv (their sh
   // strides are their own), 0 = H.  Must divide H; query head h attends over
   // K / V head h / (H / kv_heads) (torch's enable_gqa), and dk / dv are summed
@@ -199,6 +215,7 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
 // Sk <= 512, no dbias, no dropout, no key or query lengths, kv_heads == H;
 // FFK_ATTN_BWD_ONEPASS=0, read per call, turns it off), 0 = the dQ kernel
 // (which also writes delta = rowsum(dO * O)) followed by the dK/dV kernel.
+// With bias_grad set, attn_bwd_dbias_kernel follows the pair.
 // With Sk > 256 the one-pass kernel needs `ws`, an fp32 scratch of
 // attention_bwd_workspace() floats (0: the call is not eligible or needs
 // none).

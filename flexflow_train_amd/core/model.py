@@ -393,6 +393,19 @@ class FFModel:
         t._constant = True
         return t
 
+    def create_weight(self, dims, data_type=DataType.DT_FLOAT, initializer=None, name=None):
+        """A trainable tensor that layers read as a data input, e.g. a learned
+        attention bias: ``scaled_dot_product_attention(q, k, v,
+        mask=m.create_weight([1, heads, Sq, Sk]))``.  Its gradient is the sum
+        of the input gradients its readers return.  ``initializer``: one of
+        the initializer objects (default: zeros).  The parameter is named
+        ``<name>.w``."""
+        nm = self._uname(name, "weight")
+        init = initializer.to_json() if hasattr(initializer, "to_json") else (initializer or '{"type":"zero"}')
+        v = self.cg.create_weight(C.TensorShape(list(dims), C.datatype_from_string(_dt_str(data_type))), init, True,
+                                  nm + ".w")
+        return Tensor(self, v, nm + ".w")
+
     # --------------------------------------------------------------- layers
     def exp(self, x, name=None):
         return self._add("EXP", [x], name)
@@ -631,7 +644,8 @@ class FFModel:
         ``mask``: optional float tensor broadcastable to [batch, heads, Sq, Sk]
         (rank 4, every dim 1 or the full extent), added to the scores; -inf
         masks a pair.  A row with every key masked gives zeros (torch gives
-        NaN).  The mask gets no gradient.  ``causal`` excludes a mask and needs
+        NaN).  A float mask fed by something trainable (``create_weight``, a
+        projection) gets its gradient; a bool mask gets none.  ``causal`` excludes a mask and needs
         Sq == Sk.  ``dropout`` is applied to the probabilities in training.
         ``scale``: None or 0 means 1 / sqrt(D).
 

@@ -64,7 +64,12 @@ class ATenImporter:
     FFModel.  ``weights`` records {FF layer: {weight: (kind, tensor)}} for
     ``torch_fx.copy_weights`` (the same structure the fx importer uses)."""
 
-    def __init__(self, module: torch.nn.Module, example_inputs: Sequence[torch.Tensor]):
+    def __init__(self, module: torch.nn.Module, example_inputs: Sequence[torch.Tensor],
+                 fuse_attention_bias: bool = False):
+        # a scaled_dot_product_attention mask that a parameter feeds (a learned
+        # bias) as the SDPA node's fourth input, which gives it its gradient
+        # (off: the unfused chain, the default)
+        self.fuse_attention_bias = bool(fuse_attention_bias)
         was = module.training
         module.eval()
         with torch.no_grad():
@@ -457,9 +462,13 @@ class ATenImporter:
         full = (q.shape[0], q.shape[1], q.shape[2], k.shape[2])
         mt = None
         if isinstance(mask, Param):
-            return None
+            if not self.fuse_attention_bias:
+                return None
+            mask = self._weight(mask)   # a standalone weight that SDPA reads as a data input
         if isinstance(mask, FFV):
-            if mask.from_param or len(mask.shape) != 4 or any(mask.shape[i] not in (1, full[i]) for i in range(4)):
+            if mask.from_param and not self.fuse_attention_bias:
+                return None
+            if len(mask.shape) != 4 or any(mask.shape[i] not in (1, full[i]) for i in range(4)):
                 return None
             if mask.t.data_type not in (DataType.DT_FLOAT, DataType.DT_BFLOAT16, DataType.DT_HALF):
                 return None
@@ -485,8 +494,10 @@ class ATenImporter:
         constant, or an FF tensor that no parameter feeds: bool masks become
         additive 0 / -inf (not clamped: -inf is the kernels' "masked"),
         is_causal and dropout_p become attributes.  A mask that depends on a
-        parameter (a learned position bias needs a gradient, which SDPA's mask
-        does not get) and other ranks keep the unfused chain below.  That
+        parameter (a learned position bias) keeps the unfused chain below
+        unless the importer was made with ``fuse_attention_bias``: then it is
+        the SDPA node's mask like any other, grouped-query heads included, and
+        gets its gradient from the operator.  Other ranks stay unfused.  That
         chain does not expand K / V: a learned bias together with grouped-query
         heads is refused by name (it used to fail in BATCHMATMUL's shape
         inference with "batch dims mismatch")."""

@@ -74,8 +74,12 @@ class PyTorchModel:
     """Wraps an ``nn.Module`` for conversion to FlexFlow."""
 
     def __init__(self, model: nn.Module, is_hf_model: bool = False, input_names: Optional[Sequence[str]] = None,
-                 batch_size: int = 1, seq_length: Optional[int] = None):
+                 batch_size: int = 1, seq_length: Optional[int] = None, fuse_attention_bias: bool = False):
         self.model = model.eval()
+        # an F.scaled_dot_product_attention whose mask a parameter feeds (a
+        # learned bias): one SDPA node with that tensor as its fourth input
+        # when on, the unfused chain when off (the default)
+        self.fuse_attention_bias = bool(fuse_attention_bias)
         self.is_hf_model = is_hf_model
         self.input_names = list(input_names or [])
         self.batch_size = batch_size
@@ -109,7 +113,7 @@ class PyTorchModel:
             ex.append(torch.ones(list(t.dims), dtype=dt) if not dt.is_floating_point
                       else torch.randn(list(t.dims), dtype=dt))
         mod = HFWrapper(self.model, self.input_names) if self.is_hf_model else self.model
-        imp = ATenImporter(mod, ex)
+        imp = ATenImporter(mod, ex, fuse_attention_bias=self.fuse_attention_bias)
         outs = imp.to_ff(ffmodel, list(input_tensors))
         self._importer = imp
         if verbose:
@@ -418,7 +422,7 @@ def _sdpa_unfit(pm, node) -> Optional[str]:
     mask = p.get("attn_mask")
     if isinstance(mask, torch.fx.Node) and _param_fed(pm, mask, {}):
         return ("scaled_dot_product_attention with a mask that depends on a parameter: imported through "
-                "torch.export (unfused, the bias gets a gradient)")
+                "torch.export (unfused, or one SDPA node with fuse_attention_bias; the bias gets a gradient)")
     if mask is not None and p.get("is_causal"):
         return "scaled_dot_product_attention with both attn_mask and is_causal"
     return None

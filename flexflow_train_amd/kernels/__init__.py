@@ -745,6 +745,40 @@ def _attn_bias(bias, q, Sq, Sk, causal=False, kv_lens=None, q_lens=None, seg_len
     return (bias.data_ptr(), strides[0], strides[1], strides[2]), bias
 
 
+def _attn_bias_grad(bias_grad, bias, q, k, Sq, Sk):
+    """(ptr, sb, sh, sq, sk) of an attention backward's bias gradient, or ()
+    without one.  Every rule of attn_bwd_dbias_kernel is checked here, by
+    name, before anything is launched."""
+    if bias_grad is None:
+        return ()
+    B, H = q.shape[0], q.shape[2]
+    if not isinstance(bias_grad, torch.Tensor):
+        raise ValueError("attention: bias_grad must be a tensor")
+    if bias is None:
+        raise ValueError("attention: bias_grad needs a bias (it is the gradient of the call's score bias)")
+    if k.dim() == 4 and k.shape[2] != H:
+        raise ValueError(f"attention: bias_grad cannot be combined with grouped-query K / V heads (Hkv = {k.shape[2]} "
+                         f"< H = {H}); expand K / V to H heads for that call")
+    if bias_grad.dtype != torch.float32:
+        raise ValueError(f"attention: bias_grad must be fp32, got {bias_grad.dtype}")
+    if bias_grad.device != q.device:
+        raise ValueError("attention: bias_grad must be on the device of q")
+    if bias_grad.dim() != 4 or bias_grad.shape[0] not in (1, B) or bias_grad.shape[1] not in (1, H) \
+            or tuple(bias_grad.shape[2:]) != (Sq, Sk):
+        raise ValueError(f"attention: bias_grad has shape {tuple(bias_grad.shape)}, expected [1 | {B}, 1 | {H}, {Sq}, "
+                         f"{Sk}] (an extent of 1 is the sum over that axis)")
+    if Sk > 1 and bias_grad.stride(3) != 1:
+        raise ValueError("attention: the key axis (last dim) of bias_grad must be contiguous (stride 1)")
+    strides = [0 if bias_grad.shape[i] == 1 else bias_grad.stride(i) for i in range(3)]
+    if any(st % 4 or st < 0 for st in strides) or (Sq > 1 and strides[2] == 0):
+        raise ValueError(f"attention: bias_grad strides of batch / head / query must be positive multiples of 4, "
+                         f"got {strides}")
+    if bias_grad.data_ptr() % 16:
+        raise ValueError("attention: bias_grad must be 16-byte aligned")
+    STATS["attention_bias_grad"] += 1
+    return (bias_grad.data_ptr(), strides[0], strides[1], strides[2], 1)
+
+
 def _attn_gqa(q, k, v, dropout_p=0.0, kv_lens=None, q_lens=None, seg_lens=None, bias=None, dbias=None):
     """K / V head count of an attention call if it takes the GQA kernels
     (``k.shape[2]`` < H), else 0.  Every rule of the GQA kernels is checked
@@ -932,7 +966,7 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
 
 def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False,
                   dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None, q_lens=None, seg_lens=None, max_seqlen=None,
-                  seg_offsets=None, bias=None):
+                  seg_offsets=None, bias=None, bias_grad=None):
     """Flash-attention backward into dq / dk / dv; returns the path that ran
     (1: the one-pass kernel, 0: the dQ and dK/dV kernels).  ``dropout_p``,
     ``seed``, ``seed_dev``: those of the forward call that produced ``o``
@@ -951,7 +985,15 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     dv are written by its own workgroups and the rows past a pack's last
     segment as zeros.  ``bias``: the forward call's score bias (always path 0,
     no ``dbias``); a row with every key masked gets dq = 0 and adds nothing to
-    dk / dv, and no gradient is produced for the bias itself.
+    dk / dv.  ``bias_grad``: the gradient of ``bias`` (a learned bias), an fp32
+    [1 | B, 1 | H, Sq, Sk] tensor, contiguous or a view with a contiguous key
+    axis, a 16-byte aligned base and strides that are multiples of 4.  It is
+    overwritten (not accumulated) with the score gradient dS = P (keep rs dP -
+    delta) by one more launch (attn_bwd_dbias_kernel); an extent of 1 is the
+    sum over that axis, whatever the broadcast form of ``bias`` itself; the
+    entries under bias = -inf and the rows with every key masked are 0.  Needs
+    ``bias`` and Hkv == H.  Not to be confused with ``dbias``, the projection
+    bias gradients.
 
     Grouped-query attention: with k / v of Hkv < H heads (see
     ``attention_fwd``) dk / dv must be [B, Sk, Hkv, D]; each is the sum over
@@ -960,6 +1002,7 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     the forward excludes."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
+    gview = _attn_bias_grad(bias_grad, bias, q, k, Sq, Sk)
     Hkv = _attn_gqa(q, k, v, dropout_p, kv_lens, q_lens, seg_lens, bias, dbias)
     if Hkv:
         if k.shape != (B, Sk, Hkv, D) or v.shape != (B, Sk, Hkv, D):
@@ -1023,7 +1066,7 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
                                _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
                                _stream(), *dbs, ld, _p(ws), *drop, lens, **({"q_lens": qlens} if qlens else {}),
-                               **({"bias": bview} if bview else {}))
+                               **({"bias": bview} if bview else {}), **({"bias_grad": gview} if gview else {}))
     if path == 1:
         STATS["attention_bwd_onepass"] += 1
     if slab is not None:

@@ -632,13 +632,20 @@ class ScaledDotProductAttentionOp(OpImpl):
     broadcastable to [B, H, Sq, Sk] (float; -inf masks a pair; a bool mask, True
     = attend, is converted); attributes ``causal``, ``dropout`` and ``scale``
     (absent or 0: 1 / sqrt(D)).  Output [B, H, Sq, D].  A row with every key
-    masked gives zeros where torch gives NaN.  The mask gets no gradient: a
-    learned bias keeps the unfused operator chain in the importers.
+    masked gives zeros where torch gives NaN.  A float mask that something
+    trainable feeds (a learned bias) gets its gradient, the score gradient
+    summed over the axes the mask is broadcast along; a row with every key
+    masked and a pair under -inf contribute 0.  A bool mask gets none.  The
+    gradient is produced where ``ctx.extra["mask_grad"]`` is set, which the
+    executor does for a mask whose value requires a gradient.
 
     bf16 on the GPU with D in {64, 128} runs on the flash kernels, which take
     the [B, H, S, D] storage in place through [B, S, H, D] views (their
     addressing is by stride); a mask goes to their BIAS instantiations when
-    Sk % 4 == 0 and its strides allow 16-byte loads.  Dropout draws its mask
+    Sk % 4 == 0 and its strides allow 16-byte loads, and its gradient comes
+    from the flash dbias kernel (fp32 [mask batch, mask heads, Sq, Sk], summed
+    over a batch / head axis of extent 1 inside the kernel; a mask broadcast
+    over queries or keys is reduced from that in torch).  Dropout draws its mask
     from the operator's device step counter like MULTIHEAD_ATTENTION, so a
     captured step gets a new mask per replay.  Everything else (CPU, fp32,
     other head dims, Sk % 4 != 0, odd mask strides) runs _torch_attention,
@@ -677,6 +684,8 @@ class ScaledDotProductAttentionOp(OpImpl):
         if causal and Sq != Sk:
             raise ValueError(f"{ctx.name}: causal needs Sq == Sk")
         scale = float(ctx.a("scale", 0.0) or 0.0) or 1.0 / math.sqrt(D)
+        # the mask as it came in: what its gradient is shaped and typed like (a bool mask gets none)
+        mask_in = None if mask is None or mask.dtype == torch.bool else (tuple(mask.shape), mask.dtype)
         if mask is not None:
             if mask.dtype == torch.bool:
                 mask = torch.zeros(mask.shape, dtype=torch.float32, device=mask.device).masked_fill(~mask, float("-inf"))
@@ -711,19 +720,29 @@ class ScaledDotProductAttentionOp(OpImpl):
                                  _expand_kv(v, G).transpose(1, 2), causal, scale,
                                  _fallback_mask(drop, B, H, Sq, Sk), bias=mask).transpose(1, 2).contiguous()
             lse = None
-        return [o], (q, k, v, mask, o, lse, causal, scale, drop, Hkv)
+        return [o], (q, k, v, mask, o, lse, causal, scale, drop, Hkv, mask_in)
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
-        q, k, v, mask, o, lse, causal, scale, drop, Hkv = saved
+        q, k, v, mask, o, lse, causal, scale, drop, Hkv, mask_in = saved
         B, H, Sq, D = q.shape
         Sk = k.shape[2]
         G = H // Hkv
         do = grad_outputs[0]
-        tail = [None] if mask is not None else []   # the mask gets no gradient
+        need = list(need_input_grad) + [False] * 4
+        # the mask's gradient (a learned bias): the score gradient, in the
+        # mask's own batch / head form; asked for only where something reads it
+        # (``mask_grad`` in ctx.extra, set by the executor at compile time; a
+        # bare call of the operator gives the mask none, whatever need_input_grad says)
+        want_db = mask_in is not None and need[3] and bool(ctx.extra.get("mask_grad"))
+        dmask = None
         if lse is not None:
             do = do.to(q.dtype).contiguous()
             dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
             kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+            if want_db:
+                # written by the flash dbias kernel, summed there over a batch / head axis of extent 1
+                dmask = torch.empty(mask.shape[0], mask.shape[1], Sq, Sk, device=q.device, dtype=torch.float32)
+                kw["bias_grad"] = dmask
             t = lambda x: x.transpose(1, 2)
             K.attention_bwd(t(q), t(k), t(v), t(o), lse, t(do), t(dq), t(dk), t(dv), causal=causal, scale=scale,
                             bias=mask, **kw)
@@ -733,11 +752,22 @@ class ScaledDotProductAttentionOp(OpImpl):
                 dv = dv.view(B, Hkv, G, Sk, D).sum(2, dtype=torch.float32).to(q.dtype)
         else:
             qf, kf, vf = (x.detach().float().requires_grad_(True) for x in (q, k, v))
+            # the mask joins the graph: autograd sums over its broadcast axes, and
+            # a row with every key masked is filled before the softmax, so it adds 0
+            mf = mask.detach().float().requires_grad_(True) if want_db else mask
             # K / V expanded inside the graph: autograd does the group sum
             ref = _torch_attention(qf.transpose(1, 2), _expand_kv(kf, G).transpose(1, 2),
                                    _expand_kv(vf, G).transpose(1, 2), causal, scale,
-                                   _fallback_mask(drop, B, H, Sq, Sk), bias=mask)
+                                   _fallback_mask(drop, B, H, Sq, Sk), bias=mf)
             ref.float().backward(do.float().transpose(1, 2))
             dq, dk, dv = (x.grad.to(do.dtype) for x in (qf, kf, vf))
-        need = list(need_input_grad) + [False] * 3
+            if want_db:
+                dmask = mf.grad
+        if dmask is not None:
+            # the rare forms: a mask broadcast over the queries or the keys
+            for ax in (2, 3):
+                if mask_in[0][ax] == 1 and dmask.shape[ax] != 1:
+                    dmask = dmask.sum(ax, keepdim=True)
+            dmask = dmask.to(mask_in[1])
+        tail = [dmask] if mask is not None else []
         return [dq if need[0] else None, dk if need[1] else None, dv if need[2] else None] + tail

@@ -722,6 +722,10 @@ class Executor:
             need = any(rg.get(v, False) for v in s.inputs) or any(p.trainable for p in s.weights)
             for o in s.outputs:
                 rg[o] = need
+            # SDPA produces its mask's gradient (a learned attention bias) only
+            # where something trainable feeds the mask: one more kernel launch
+            if s.op_type == "SDPA" and len(s.inputs) > 3:
+                s.ctx.extra["mask_grad"] = bool(rg.get(s.inputs[3], False))
             for p in s.weights:
                 p.n_consumers += 1
                 if p.final_step < 0:

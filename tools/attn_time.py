@@ -11,6 +11,9 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
     python tools/attn_time.py --packed [--dropout 0.1]                (packed sequences against the padded batch)
     python tools/attn_time.py --bias key|full                         (additive mask / bias against no bias, kv_lens
                                                                        and the unfused operator chain)
+    python tools/attn_time.py --bias-grad                             (gradient of a learned [1, H, Sq, Sk] bias:
+                                                                       the backward with and without bias_grad, and
+                                                                       the SDPA node against the unfused chain)
     python tools/attn_time.py --gqa G                                 (grouped-query K / V heads, H / G of them,
                                                                        against the expanded call and the H-head call)
 
@@ -341,6 +344,73 @@ def bias_ab(kind, iters, rounds=5, seed=0):
         print(json.dumps(rec), flush=True)
 
 
+def bias_grad_ab(iters, rounds=5):
+    """Interleaved same-process timing of a learned bias [1, H, Sq, Sk] at the
+    BERT-large and GPT-3-medium shapes (non-causal: the BIAS kernels have no
+    causal form).  Kernel level: the backward with the bias, without and with
+    ``bias_grad`` (the extra launch of attn_bwd_dbias_kernel, which sums over
+    the batch).  Model level, through the executor: forward + backward of one
+    SDPA node whose mask is a ``create_weight`` tensor, against the unfused
+    chain (TRANSPOSE, BATCHMATMUL, SCALAR_MULTIPLY, EW_ADD, SOFTMAX,
+    BATCHMATMUL) reading the same weight.  `dbias_workgroups`: the new
+    kernel's grid against the 256 CUs."""
+    import statistics
+
+    from flexflow_train_amd.core import DataType, FFConfig, FFModel, LossType, SGDOptimizer
+
+    def model(B, S, H, D, fused):
+        m = FFModel(FFConfig())
+        q, k, v = (m.create_tensor([B, H, S, D], DataType.DT_FLOAT, name=n) for n in "qkv")
+        w = m.create_weight([1, H, S, S], name="bias")
+        if fused:
+            m.scaled_dot_product_attention(q, k, v, mask=w, name="attn")
+        else:
+            sc = m.batch_matmul(q, m.transpose(k, [0, 1, 3, 2], name="kt"), name="qk")
+            sc = m.add(m.scalar_multiply(sc, 1.0 / D ** 0.5, name="scale"), w, name="mask")
+            m.batch_matmul(m.softmax(sc, 3, name="softmax"), v, name="attn")
+        m.compile(optimizer=SGDOptimizer(m, lr=0.0), loss_type=LossType.LOSS_MEAN_SQUARED_ERROR_AVG_REDUCE)
+        return m.executor
+
+    for name in ("bert-large", "gpt3-medium"):
+        B, S, H, D, _ = SHAPES[name]
+        g = torch.Generator(device="cuda").manual_seed(0)
+        qkv = torch.randn(B, S, 3, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+        do = torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g)
+        dqkv = torch.empty_like(qkv)
+        bias = 2 * torch.randn(1, H, S, S, device="cuda", generator=g)
+        dbias = torch.empty_like(bias)
+        o, lse = K.attention_fwd(q, k, v, bias=bias)
+        feeds = {n: t.transpose(1, 2).float().contiguous() for n, t in (("q", q), ("k", k), ("v", v))}
+        dout = do.transpose(1, 2).contiguous()
+        exs = {"sdpa": model(B, S, H, D, True), "unfused": model(B, S, H, D, False)}
+        for ex in exs.values():
+            ex.set_parameter("bias.w", bias.cpu())
+
+        def step(ex):
+            ex.forward(feeds, training=True)
+            ex.backward(dout)
+
+        t = {}
+        for _ in range(rounds):
+            for tag, kw in (("bwd", {}), ("bwd_bias_grad", dict(bias_grad=dbias))):
+                t.setdefault(tag, []).append(_time(
+                    lambda: K.attention_bwd(q, k, v, o, lse, do, dqkv[:, :, 0], dqkv[:, :, 1], dqkv[:, :, 2], bias=bias,
+                                            **kw), iters))
+            for tag, ex in exs.items():
+                t.setdefault("step_" + tag, []).append(_time(lambda: step(ex), max(3, iters // 5)))
+        med = {key: statistics.median(x) for key, x in t.items()}
+        rec = {"shape": name + " non-causal", "bias_shape": list(bias.shape), "iters": iters, "rounds": rounds,
+               "dbias_workgroups": H * ((S + 127) // 128) * ((S + 63) // 64), "cus": 256}
+        for key, xs in t.items():
+            rec[key + "_ms"] = round(med[key], 4)
+            rec[key + "_rounds"] = [round(x, 4) for x in xs]
+        rec["dbias_kernel_ms"] = round(med["bwd_bias_grad"] - med["bwd"], 4)
+        rec["bias_grad_over_bwd"] = round(med["bwd_bias_grad"] / med["bwd"], 3)
+        rec["unfused_over_sdpa"] = round(med["step_unfused"] / med["step_sdpa"], 2)
+        print(json.dumps(rec), flush=True)
+
+
 GQA_SHAPES = {"b4-h32-d128-s2048-causal": (4, 2048, 32, 128, True), "b8-h16-d64-s2048-causal": (8, 2048, 16, 64, True)}
 
 
@@ -418,6 +488,8 @@ def gqa_ab(G, iters, rounds=5):
 def main():
     if "--gqa" in sys.argv:            # grouped-query K / V heads against the expanded and the H-head call
         return gqa_ab(int(sys.argv[sys.argv.index("--gqa") + 1]), 200)
+    if "--bias-grad" in sys.argv:      # gradient of a learned bias: the extra launch, and SDPA against the unfused chain
+        return bias_grad_ab(30)
     if "--bias" in sys.argv:           # additive mask / bias against no bias, kv_lens and the unfused chain
         kind = sys.argv[sys.argv.index("--bias") + 1]
         if kind not in ("key", "full"):
