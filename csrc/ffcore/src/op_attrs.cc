@@ -846,6 +846,10 @@ OpSpec mha_spec() {
 // shards then keep h / G local (shard j holds query heads [j H / d, ...) and
 // K / V heads [j Hkv / d, ...)).
 bool sdpa_has_mask(const OpAttrs& a) { return a.has("mask") && a.b("mask"); }
+// Sliding-window causal attention: attribute window = W >= 1 (absent: none, and
+// graphs without it serialise as they did): key k is visible to query q iff
+// 0 <= q - k < W.  Needs causal.
+int64_t sdpa_window(const OpAttrs& a) { return a.has("window") ? a.i("window") : 0; }
 
 OpSpec sdpa_spec() {
   OpSpec s;
@@ -877,6 +881,10 @@ OpSpec sdpa_spec() {
         require(m.dims[d] == full[d] || m.dims[d] == 1, a, "every mask dim must be 1 or the full extent");
     }
     if (a.b("causal")) require(q.dims[2] == k.dims[2], a, "causal needs Sq == Sk");
+    if (a.has("window")) {
+      require(a.i("window") >= 1, a, "window must be >= 1");
+      require(a.b("causal"), a, "window needs causal (bidirectional windows are not offered)");
+    }
     return Shapes{q};
   };
   s.wts = no_weight_shapes;
@@ -1759,6 +1767,8 @@ OpWork estimate_op_work(const OpAttrs& a, const std::vector<TensorShape>& in,
       double d = static_cast<double>(in[0].dims[3]);
       r.flops = 4 * b * h * sq * sk * d;
       if (a.b("causal")) r.flops -= 2 * b * h * sq * sk * d;
+      // a window: at most min(W, Sk) keys per query, an upper bound (the first W rows see fewer)
+      if (sdpa_window(a) > 0) r.flops = std::min(r.flops, 4 * b * h * sq * std::min(static_cast<double>(sdpa_window(a)), sk) * d);
       r.matmul_like = true;
       r.mfma_efficiency_hint = 0.8;
       break;

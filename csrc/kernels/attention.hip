@@ -32,7 +32,8 @@
 //
 // Kernels: attn_fwd_kernel, attn_bwd_dq_kernel and attn_bwd_dkdv_kernel, each
 // for D in {64, 128} x CAUSAL x DROP x VARLEN (and, with VARLEN, PACKED) plus
-// D x DROP with BIAS and D x CAUSAL with GQA, attn_bwd_onepass_kernel, and
+// D x DROP with BIAS, D x CAUSAL with GQA and D x GQA with WINDOW (causal),
+// attn_bwd_onepass_kernel, and
 // attn_bwd_dbias_kernel for D x DROP (the bias gradient, after the BIAS pair);
 // attention_fwd / attention_bwd pick one through with_head and
 // with_features.  Packed calls also launch
@@ -192,6 +193,36 @@
 // GQA excludes dropout, kv_lens, q_lens, seg_offsets, bias and the fused dbias
 // (std::invalid_argument), and its backward is always the dQ + dK/dV pair.  A
 // call with Hkv == H runs the GQA = false kernels, the code they were.
+//
+// Sliding-window causal attention (WINDOW instantiations of the forward, dQ
+// and dK/dV kernels, D in {64, 128} with and without GQA, only with CAUSAL =
+// true and DROP = VARLEN = PACKED = BIAS = false; AttnTensors::window = W).
+// Key k is visible to query q iff 0 <= q - k < W: the W most recent positions,
+// the query's own included, so every row has a key and a finite LSE.
+//  * forward and dQ: a 128-query block walks the 64-key tiles from t_lo =
+//    max(0, q_blk - W + 1) / 64 to where causal ends; the first staged tile is
+//    t_lo and the LDS double buffer runs over t - t_lo.  A wave (rows qw ..
+//    qw + 31) is active on a tile iff k0 <= qw + 31 and k0 + 63 >= qw - W + 1,
+//    a wave-uniform branch like the causal one; the element mask runs on the
+//    tiles that cross the diagonal or the left edge of the wave's highest row
+//    ((qw + 31) - W + 1 > k0), the interior tiles keep the unmasked pass.
+//  * the rows of a wave have left edges up to 31 keys apart, so with a small
+//    W a row's whole share of the wave's first active tile can be masked: it
+//    keeps m = -inf and l = 0 through that tile, and the m == -inf guards of
+//    the rescale (those of the BIAS and VARLEN rows) keep exp2(-inf + inf) out.
+//  * dK/dV: a 128-key block walks the 64-query tiles from the diagonal to
+//    min(Sq, k_blk + 128 + W - 1); a wave is active iff the tile has a pair
+//    with 0 <= q - key < W and masks the tiles that straddle q - key = W.
+//    With GQA every head of the group walks the same tile range in the flat
+//    (head, tile) sequence; dK / dV still round once.  No Sq x Sk object, no
+//    atomics, no workspace: two calls give equal bits.
+//  * W >= Sk is plain causal attention: make_params clears the window and the
+//    call runs the CAUSAL kernels, bit-equal to a call without one.
+//  * no WINDOW kernel has scratch; registers, LDS and occupancy per
+//    instantiation are in profiles/attn_window_isa.txt.
+// WINDOW needs causal and excludes dropout, kv_lens, q_lens, seg_offsets, bias,
+// bias_grad and the fused dbias (std::invalid_argument), and its backward is
+// always the dQ + dK/dV pair.
 #include <cstdlib>
 #include <type_traits>
 
@@ -233,6 +264,9 @@ struct AttnParams {
   // packed sequences (PACKED kernels only; B = packs, Sq = Sk = max_seqlen)
   const int32_t* seg_off;   // [B, M, 2]: clamped (start, len) of segment (n, m), from attn_segment_offsets_kernel
   int M, T;                 // segment slots per pack; physical tokens per pack
+  // sliding window (WINDOW kernels only): key k is visible to query q iff 0 <= q - k < window.  Here and not
+  // at the end: Hkv / G stay the last words, next to the hidden kernel arguments the GQA kernels load with them
+  int window;
   // additive score bias (BIAS kernels only): fp32, the key axis contiguous
   const float* bias;
   int64_t bias_sb, bias_sh, bias_sq;  // element strides of batch / head / query, 0 = broadcast
@@ -488,8 +522,16 @@ __device__ __forceinline__ void bias_partial(const f32x16 (&acc)[DT], float mul,
 // BIAS at D = 128: one wave per SIMD.  At two (256 registers, of which the
 // unbiased form takes 246) the tile's 32 bias values spilled and were
 // reloaded inside the tile loop (68 - 188 bytes of scratch).
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false>
+// WINDOW (with CAUSAL): the tile loop starts at the first tile that row q_blk
+// of the block sees (t_lo); the staging and the double buffer run over
+// t - t_lo.  A wave skips the tiles left of its lowest row's window as it
+// skips those right of the diagonal, and masks q - key >= window on the tiles
+// that cross the left edge of its highest row.  A row whose share of the
+// wave's first active tile is all masked keeps m = -inf, l = 0 through it; the
+// m == -inf guards of the rescale serve it as they serve BIAS and VARLEN rows.
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false, bool WINDOW = false>
 __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kernel(AttnParams P) {
+  static_assert(!WINDOW || (CAUSAL && !DROP && !VARLEN && !PACKED && !BIAS), "WINDOW: causal, and no other axis but GQA");
   constexpr int KS = D / 16;        // k-steps over the head dim
   constexpr int DT = D / 32;        // 32-wide output tiles over the head dim
   constexpr int KV = 64;            // keys per tile
@@ -550,13 +592,16 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
 
   int n_tiles = (Skl + KV - 1) / KV;
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
+  // window: the first tile with a key that the block's first row sees
+  [[maybe_unused]] int t_lo = 0;
+  if constexpr (WINDOW) t_lo = max(q_blk - P.window + 1, 0) / KV;
   // bias: this query's row, at the lane half's first key
   [[maybe_unused]] const float* brow = nullptr;
   if constexpr (BIAS) brow = P.bias + b * P.bias_sb + hh * P.bias_sh + static_cast<int64_t>(q) * P.bias_sq + 4 * h;
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, pn, hk, 0, Skl, ps);
-  vl.load(P.v, pn, hk, 0, Skl, ps);
+  kl.load(P.k, pn, hk, WINDOW ? t_lo * KV : 0, Skl, ps);
+  vl.load(P.v, pn, hk, WINDOW ? t_lo * KV : 0, Skl, ps);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -607,16 +652,18 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
     bmul = P.inv_scale_log2 * kLog2e;  // 1 / scale
     load_bias(0);
   }
-  for (int t = 0; t < n_tiles; ++t) {
+  for (int t = WINDOW ? t_lo : 0; t < n_tiles; ++t) {
     const int k0 = t * KV;
-    const unsigned char* Kt = smem + (t & 1) * 2 * TILE_BYTES;
+    const int tb = WINDOW ? t - t_lo : t;  // the tile's place in the double buffer
+    const unsigned char* Kt = smem + (tb & 1) * 2 * TILE_BYTES;
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
     if (has_next) {  // issue next tile's HBM loads before this tile's MFMAs
       kl.load(P.k, pn, hk, k0 + KV, Skl, ps);
       vl.load(P.v, pn, hk, k0 + KV, Skl, ps);
     }
-    const bool wave_active = !CAUSAL || (k0 <= qw + 31);
+    // window: also not wholly left of the window of the wave's lowest row
+    const bool wave_active = !CAUSAL || (k0 <= qw + 31 && (!WINDOW || k0 + KV - 1 > qw - P.window));
     if (wave_active) {
       // ---- S^T[key][q] for two 32-key tiles
       f32x16 s[2];
@@ -635,14 +682,16 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
       // ---- mask (only tiles that cross the sequence end or the causal
       // diagonal — a wave-uniform branch), tile max of the RAW scores: the
       // softmax scale is folded into one FMA per score inside exp2 below
-      const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw);
+      // (window: or the left edge of the wave's highest row)
+      const bool need_mask =
+          (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (WINDOW && qw + 31 - P.window >= k0);
       if (need_mask) {
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + kt * 32 + acc_row(r) + 4 * h;
-            if (key >= Skl || (CAUSAL && key > q)) s[kt][r] = -INFINITY;
+            if (key >= Skl || (CAUSAL && key > q) || (WINDOW && q - key >= P.window)) s[kt][r] = -INFINITY;
           }
       }
       // two independent v_max3 chains over the 32 scores (16 issues)
@@ -708,7 +757,7 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
       if (has_next) load_bias(k0 + KV);
     }
     if (has_next) {
-      unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
+      unsigned char* nxt = smem + ((tb + 1) & 1) * 2 * TILE_BYTES;
       kl.store(nxt);
       vl.store(nxt + TILE_BYTES);
     }
@@ -763,8 +812,11 @@ __global__ __launch_bounds__(256, (BIAS && D == 128 ? 1 : 2)) void attn_fwd_kern
 // accumulates bq^T = K^T P^T from the K^T fragments of the dQ product (one
 // more MFMA product, DT more accumulators), and the epilogue adds
 // (dlt - delta) bq^T to dQ^T and writes delta for the dK / dV kernel.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false>
+// WINDOW: the forward's tile range, wave test and left-edge mask (P = 0 where
+// q - key >= window); P comes from the stored lse, so there is no running max.
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false, bool WINDOW = false>
 __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 1)) void attn_bwd_dq_kernel(AttnParams P) {
+  static_assert(!WINDOW || (CAUSAL && !DROP && !VARLEN && !PACKED && !BIAS), "WINDOW: causal, and no other axis but GQA");
   constexpr int KS = D / 16, DT = D / 32, KV = 64;
   constexpr int TILE_BYTES = KV * D * 2;
   constexpr bool XDELTA = VARLEN && DROP;  // delta from the probabilities (comment above)
@@ -856,10 +908,13 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
 
   int n_tiles = (Skl + KV - 1) / KV;
   if (CAUSAL) n_tiles = min(n_tiles, (q_blk + 128 + KV - 1) / KV);
+  // window: the first tile with a key that the block's first row sees
+  [[maybe_unused]] int t_lo = 0;
+  if constexpr (WINDOW) t_lo = max(q_blk - P.window + 1, 0) / KV;
 
   TileLoader<D, KV> kl, vl;
-  kl.load(P.k, pn, hk, 0, Skl, ps);
-  vl.load(P.v, pn, hk, 0, Skl, ps);
+  kl.load(P.k, pn, hk, WINDOW ? t_lo * KV : 0, Skl, ps);
+  vl.load(P.v, pn, hk, WINDOW ? t_lo * KV : 0, Skl, ps);
   kl.store(smem);
   vl.store(smem + TILE_BYTES);
   __syncthreads();
@@ -890,9 +945,10 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
       else n_tiles = 0;
     }
   }
-  for (int t = SKIP_BY_START ? t_first : 0; t < n_tiles; ++t) {
+  for (int t = SKIP_BY_START ? t_first : (WINDOW ? t_lo : 0); t < n_tiles; ++t) {
     const int k0 = t * KV;
-    const unsigned char* Kt = smem + (t & 1) * 2 * TILE_BYTES;
+    const int tb = WINDOW ? t - t_lo : t;  // the tile's place in the double buffer
+    const unsigned char* Kt = smem + (tb & 1) * 2 * TILE_BYTES;
     const unsigned char* Vt = Kt + TILE_BYTES;
     const bool has_next = t + 1 < n_tiles;
     // bias of this tile, issued ahead of the next tile's K / V loads (see the
@@ -907,8 +963,9 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
       kl.load(P.k, pn, hk, k0 + KV, Skl, ps);
       vl.load(P.v, pn, hk, k0 + KV, Skl, ps);
     }
-    const bool wave_active = !CAUSAL || (k0 <= qw + 31);
-    const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= (VARLEN ? Sql : P.Sq));
+    const bool wave_active = !CAUSAL || (k0 <= qw + 31 && (!WINDOW || k0 + KV - 1 > qw - P.window));
+    const bool need_mask = (k0 + KV > Skl) || (CAUSAL && k0 + KV - 1 > qw) || (qw + 31 >= (VARLEN ? Sql : P.Sq)) ||
+                           (WINDOW && qw + 31 - P.window >= k0);
     if (wave_active) {
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
@@ -937,7 +994,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
           for (int r = 0; r < 16; ++r) {
             const int key = k0 + kt * 32 + acc_row(r) + 4 * h;
             float pv = fexp2(s[r] * P.scale_log2 - lse);
-            if (key >= Skl || (CAUSAL && key > q) || !q_live) pv = 0.f;
+            if (key >= Skl || (CAUSAL && key > q) || (WINDOW && q - key >= P.window) || !q_live) pv = 0.f;
             if constexpr (XDELTA) {
               const float kd = kept(dp[r], k0, kt, r);
               pf[r >> 3][r & 7] = f2bf(pv);
@@ -979,7 +1036,7 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
       }
     }
     if (has_next) {
-      unsigned char* nxt = smem + ((t + 1) & 1) * 2 * TILE_BYTES;
+      unsigned char* nxt = smem + ((tb + 1) & 1) * 2 * TILE_BYTES;
       kl.store(nxt);
       vl.store(nxt + TILE_BYTES);
     }
@@ -1014,8 +1071,14 @@ __global__ __launch_bounds__(256, (D == 64 ? (CAUSAL || DROP || BIAS ? 2 : 3) : 
 // hash index q * Sk + key steps by Sk per register; the dP accumulator starts
 // from zero and -delta is added after the keep scale (dS = P (keep rs dP -
 // delta)); dV takes keep . P and rs at the store.
-template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false>
+// WINDOW: the query-tile loop of a key block ends at the last tile with a
+// query that sees the block's last key, min(Sq, k_blk + 128 + window - 1); a
+// wave skips the tiles whose queries are all past its keys' windows and masks
+// q - key >= window on the tiles that straddle that edge.  With GQA every head
+// of the group walks the same [t0, n_q_tiles) range.
+template <int D, bool CAUSAL, bool DROP, bool VARLEN, bool PACKED, bool BIAS, bool GQA = false, bool WINDOW = false>
 __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv_kernel(AttnParams P) {
+  static_assert(!WINDOW || (CAUSAL && !DROP && !VARLEN && !PACKED && !BIAS), "WINDOW: causal, and no other axis but GQA");
   constexpr int KS = D / 16, DT = D / 32, QT = 64, KW = 32;
   // prefetched LDS fragments (below): GPT causal shape 0.341 -> 0.333 ms, BERT
   // within noise (profiles/ab_attn_bwd_pf_r3.txt).  At D = 128 (one wave /
@@ -1085,7 +1148,10 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
   // VARLEN: a key block wholly past the length skips the query loop and
   // stores zeros (dK = dV = 0, and zero partials into the dbias slab); the
   // loop of a live block ends at the sample's last live query tile
-  const int n_q_tiles = (VARLEN && k_blk >= Skl()) ? 0 : (Sql() + QT - 1) / QT;
+  // (window: at the last tile that sees the block's last key)
+  const int n_q_tiles = (VARLEN && k_blk >= Skl())
+                            ? 0
+                            : ((WINDOW ? min(Sql(), k_blk + 4 * KW + P.window - 1) : Sql()) + QT - 1) / QT;
   const int t0 = CAUSAL ? (k_blk / QT) : 0;
   // GQA: this workgroup serves the G query heads hh * G .. of its K / V head,
   // one after another, as ONE sequence of (head, query tile) steps: t runs
@@ -1211,8 +1277,9 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
       dl.load(P.dout, pn, hh, q0 + QT, Sql(), ps);
       fetch_scalars(q0 + QT);
     }
-    const bool wave_active = !CAUSAL || (q0 + QT - 1 >= kw);
-    const bool need_mask = (q0 + QT > Sql()) || (CAUSAL && q0 < kw + KW - 1) || (kw + KW - 1 >= Skl());
+    const bool wave_active = !CAUSAL || (q0 + QT - 1 >= kw && (!WINDOW || q0 - (kw + KW - 1) < P.window));
+    const bool need_mask = (q0 + QT > Sql()) || (CAUSAL && q0 < kw + KW - 1) || (kw + KW - 1 >= Skl()) ||
+                           (WINDOW && q0 + QT - 1 - kw >= P.window);
     if (wave_active) {
       // DROP at D = 128 (all 512 registers in use): the fragment offsets of
       // the per-pair reads are derived from the lane id again in every tile.
@@ -1291,7 +1358,7 @@ __global__ __launch_bounds__(256, (D == 64 && !BIAS ? 2 : 1)) void attn_bwd_dkdv
             float e = s[r] * P.scale_log2;
             if constexpr (BIAS) e = fmaf(s[r], P.scale_log2, bb[qt * 16 + r] * kLog2e);
             float pv = fexp2(e);
-            if (qq >= Sql() || (CAUSAL && key > qq) || !k_ok) pv = 0.f;
+            if (qq >= Sql() || (CAUSAL && key > qq) || (WINDOW && qq - key >= P.window) || !k_ok) pv = 0.f;
             s[r] = pv;
             dp[r] = pv * dp[r];
           }
@@ -1942,6 +2009,18 @@ static AttnParams make_params(const AttnTensors& t, int B, int H, int Sq, int Sk
   }
   P.kv_lens = t.kv_lens;
   P.q_lens = t.q_lens;
+  if (t.window) {
+    // the WINDOW kernels exist with causal and without any other axis but GQA
+    if (t.window < 0) throw std::invalid_argument("attention: window must be >= 1 (0: no window)");
+    if (!causal_grid) throw std::invalid_argument("attention: window needs causal (bidirectional windows are not served)");
+    if (t.drop_threshold) throw std::invalid_argument("attention: window excludes dropout");
+    if (t.kv_lens || t.q_lens) throw std::invalid_argument("attention: window excludes kv_lens / q_lens");
+    if (t.seg_offsets) throw std::invalid_argument("attention: window excludes packed sequences (seg_lens)");
+    if (t.bias.p || t.bias_grad.p) throw std::invalid_argument("attention: window excludes bias / bias_grad");
+    if (t.dbq || t.dbk || t.dbv) throw std::invalid_argument("attention: window excludes the fused dbias");
+    // a window that covers every key is plain causal attention, on its kernels
+    P.window = t.window >= Sk ? 0 : t.window;
+  }
   if (t.seg_offsets) {
     // packed sequences: B packs of seg_T tokens, Sq = Sk = max_seqlen
     if (t.kv_lens || t.q_lens)
@@ -2066,6 +2145,15 @@ void attention_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, fl
     with_features(P.drop_thr != 0, P.kv_lens || P.q_lens || packed, [&](auto dr, auto vl) {
       constexpr int DD = decltype(d)::value;
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
+      if constexpr (CC && !DR && !VL) {
+        if (P.window) {  // make_params: causal, no dropout, lengths, packing or bias
+          if (P.G > 1)
+            hipLaunchKernelGGL((attn_fwd_kernel<DD, true, false, false, false, false, true, true>), grid, block, 0, st, P);
+          else
+            hipLaunchKernelGGL((attn_fwd_kernel<DD, true, false, false, false, false, false, true>), grid, block, 0, st, P);
+          return;
+        }
+      }
       if constexpr (!DR && !VL) {
         if (P.G > 1) {  // make_params: no dropout, lengths, packing or bias
           hipLaunchKernelGGL((attn_fwd_kernel<DD, CC, false, false, false, false, true>), grid, block, 0, st, P);
@@ -2126,6 +2214,21 @@ int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, flo
     with_features(drop, varlen, [&](auto dr, auto vl) {
       constexpr int DD = decltype(d)::value;
       constexpr bool CC = decltype(c)::value, DR = decltype(dr)::value, VL = decltype(vl)::value;
+      if constexpr (CC && !DR && !VL) {
+        if (P.window) {
+          const dim3 gkv(static_cast<unsigned>(B * P.Hkv), nk);  // GQA: dK/dV over the B * Hkv K / V heads
+          if (P.G > 1) {
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, true, false, false, false, false, true, true>), gq, block, 0, st, P);
+            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, true, false, false, false, false, true, true>), gkv, block, 0, st,
+                               P);
+          } else {
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<DD, true, false, false, false, false, false, true>), gq, block, 0, st, P);
+            hipLaunchKernelGGL((attn_bwd_dkdv_kernel<DD, true, false, false, false, false, false, true>), gk, block, 0, st,
+                               P);
+          }
+          return;
+        }
+      }
       if constexpr (!DR && !VL) {
         if (P.G > 1) {
           // dQ over the B * H query heads, dK/dV over the B * Hkv K / V heads

@@ -203,6 +203,16 @@ struct AttnTensors {
   // the fused dbias (std::invalid_argument).  kv_heads == H (or 0) is the
   // call without it, on the same kernels.
   int kv_heads = 0;
+  // sliding-window causal attention: key k is visible to query q iff
+  // 0 <= q - k < window, the `window` most recent positions with the query's
+  // own (Hugging Face Mistral's sliding_window).  0 = none.  The kernels skip
+  // the key tiles left of a query block's window (forward, dQ) and the query
+  // tiles past a key block's (dK/dV): O(S * window) work.  Needs causal;
+  // goes with kv_heads < H; excludes dropout, kv_lens, q_lens, seg_offsets,
+  // bias, bias_grad and the fused dbias (std::invalid_argument).  window >= Sk
+  // is plain causal attention and runs its kernels.  Always the dQ + dK/dV
+  // kernel pair.
+  int window = 0;
 };
 // seg_lens int32 [N, M] -> seg_off int32 [N, M, 2], both on the device: start =
 // sum of the pack's earlier clamped lengths, len clamped to [0, min(max_seqlen,

@@ -630,7 +630,8 @@ class FFModel:
                          bias=bias, add_bias_kv=add_bias_kv, add_zero_attn=add_zero_attn, causal=causal,
                          seq_parallel_mode=seq_parallel_mode, **extra)
 
-    def scaled_dot_product_attention(self, q, k, v, mask=None, causal=False, dropout=0.0, scale=None, name=None):
+    def scaled_dot_product_attention(self, q, k, v, mask=None, causal=False, dropout=0.0, scale=None, name=None,
+                                     window=None):
         """Attention without projections (the ``SDPA`` operator):
         softmax(scale * q k^T + mask) v for ``q`` [batch, heads, Sq, D] and
         ``k`` / ``v`` [batch, heads, Sk, D]; the result is [batch, heads, Sq, D].
@@ -654,10 +655,20 @@ class FFModel:
         torch fallback of the same definition.  With kv_heads < heads the
         unmasked, undropped case runs GQA kernels in place on the kv_heads
         storage; with a mask or dropout K / V are expanded to ``heads`` heads
-        once and the existing kernels run."""
+        once and the existing kernels run.
+
+        ``window``: sliding-window causal attention, an integer W >= 1 (None
+        or 0: none; needs ``causal``): key k is visible to query q iff
+        0 <= q - k < W, the W most recent positions with the query's own
+        (Hugging Face Mistral's ``sliding_window``).  The flash case without
+        dropout runs window kernels that skip the tiles outside the band, in
+        place on the kv_heads storage; the rest takes the fallback."""
         inputs = [q, k, v] + ([mask] if mask is not None else [])
+        if window is not None and int(window) < 0:
+            raise ValueError("scaled_dot_product_attention: window must be >= 1")
+        extra = {"window": int(window)} if window else {}   # absent by default: existing graphs serialise as before
         return self._add("SDPA", inputs, name, causal=bool(causal), dropout=float(dropout),
-                         scale=float(scale or 0.0), mask=mask is not None)
+                         scale=float(scale or 0.0), mask=mask is not None, **extra)
 
     def experts(self, input, expert_ids, gate_weights, num_experts, hidden_size, out_dim=None,
                 activation=ActiMode.AC_MODE_RELU, use_bias=True, expert_parallel_mode="replicated", name=None):

@@ -634,11 +634,12 @@ def string_to_ff(lines: Sequence[str], ffmodel, input_tensors: Sequence):
         elif op == "MULTIHEAD_ATTENTION":
             q, k, v = (env[n] for n in ins[:3])
             env[name] = f.multihead_attention(q, k, v, int(a[0]), int(a[1]), name=name)
-        elif op == "SDPA":   # causal; dropout; scale (0: 1 / sqrt(D)); has mask (the fourth input)
+        elif op == "SDPA":   # causal; dropout; scale (0: 1 / sqrt(D)); has mask (the fourth input); [window]
             q, k, v = (env[n] for n in ins[:3])
             env[name] = f.scaled_dot_product_attention(q, k, v, mask=env[ins[3]] if int(a[3]) else None,
                                                        causal=bool(int(a[0])), dropout=float(a[1]),
-                                                       scale=float(a[2]) or None, name=name)
+                                                       scale=float(a[2]) or None, name=name,
+                                                       window=int(a[4]) if len(a) > 4 else None)
         elif op == "SPLIT":
             import ast
 

@@ -803,6 +803,28 @@ def _attn_gqa(q, k, v, dropout_p=0.0, kv_lens=None, q_lens=None, seg_lens=None, 
     return Hkv
 
 
+def _attn_window(window, causal, Sk, dropout_p=0.0, kv_lens=None, q_lens=None, seg_lens=None, bias=None, dbias=None,
+                 bias_grad=None):
+    """The window of an attention call that takes the WINDOW kernels, else 0
+    (``window`` None, or >= Sk: plain causal attention, the call without it).
+    Every rule of the WINDOW kernels is checked here, by name, before anything
+    is launched."""
+    if window is None:
+        return 0
+    W = int(window)
+    if W < 1:
+        raise ValueError(f"attention: window must be >= 1, got {window}")
+    if not causal:
+        raise ValueError("attention: window needs causal=True (bidirectional windows are not supported)")
+    for what, on in (("dropout_p", float(dropout_p) > 0.0), ("kv_lens", kv_lens is not None),
+                     ("q_lens", q_lens is not None), ("packed sequences (seg_lens)", seg_lens is not None),
+                     ("bias", bias is not None), ("bias_grad", bias_grad is not None),
+                     ("the fused dbias", dbias is not None)):
+        if on:
+            raise ValueError(f"attention: window cannot be combined with {what}")
+    return W if W < Sk else 0
+
+
 def attention_segment_offsets(seg_lens, T: int, max_seqlen: Optional[int] = None):
     """Clamped (start, len) of every segment of a packed batch: int32
     [N, M, 2] from ``seg_lens`` int32 [N, M], computed on the device (no host
@@ -862,7 +884,7 @@ def _attn_packed(seg_lens, max_seqlen, seg_offsets, q, k, v, kv_lens, q_lens, db
 
 
 def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None,
-                  q_lens=None, seg_lens=None, max_seqlen=None, seg_offsets=None, bias=None):
+                  q_lens=None, seg_lens=None, max_seqlen=None, seg_offsets=None, bias=None, window=None):
     """Flash attention forward.  q,k,v: [B, S, H, D] bf16 views (any b/s/h
     strides, e.g. slices of a packed [B, S, 3, H, D] QKV buffer).
     Returns (o [B, Sq, H, D] contiguous, lse [B, H, Sq] fp32 log2-domain).
@@ -874,6 +896,14 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     equal those of a call on K / V expanded to H heads bit for bit.  Excludes
     ``dropout_p``, ``kv_lens`` / ``q_lens``, ``seg_lens`` and ``bias``
     (ValueError).  Hkv == H is the call without it, on the same kernels.
+
+    ``window``: sliding-window causal attention.  An integer W >= 1: key k is
+    visible to query q iff 0 <= q - k < W, the W most recent positions with
+    the query's own (Hugging Face Mistral's ``sliding_window``).  The kernels
+    skip the key tiles outside the band, O(S * W) work.  Needs ``causal``;
+    goes with grouped-query K / V; excludes ``dropout_p``, ``kv_lens`` /
+    ``q_lens``, ``seg_lens`` and ``bias`` (ValueError).  W >= Sk is plain
+    causal attention: the call without ``window``, bit for bit.
 
     ``dropout_p`` > 0: dropout on the attention probabilities inside the
     kernel; the mask is that of ``ops.attention.attention_dropout_mask`` for
@@ -921,17 +951,21 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     Sk = k.shape[1]
     if D not in (64, 128):
         raise ValueError("attention: head dim must be 64 or 128")
+    W = _attn_window(window, causal, Sk, dropout_p, kv_lens, q_lens, seg_lens, bias)
     Hkv = _attn_gqa(q, k, v, dropout_p, kv_lens, q_lens, seg_lens, bias)
-    if Hkv:
-        if k.shape != (B, Sk, Hkv, D) or v.shape != (B, Sk, Hkv, D):
+    if Hkv or W:
+        if k.shape != (B, Sk, Hkv or H, D) or v.shape != (B, Sk, Hkv or H, D):
             raise ValueError("attention: q/k/v shape mismatch")
         if out is None:
             out = torch.empty(B, Sq, H, D, device=q.device, dtype=q.dtype)
         lse = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
         sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
         ext().attention_fwd(_view4(q), _view4(k), _view4(v), _view4(out), lse.data_ptr(), B, H, Sq, Sk, D, sc,
-                            bool(causal), _stream(), kv_heads=Hkv)
-        STATS["attention_gqa"] += 1
+                            bool(causal), _stream(), kv_heads=Hkv, **({"window": W} if W else {}))
+        if Hkv:
+            STATS["attention_gqa"] += 1
+        if W:
+            STATS["attention_window"] += 1
         STATS["attention_fwd"] += 1
         return out, lse
     bview, bkeep = _attn_bias(bias, q, Sq, Sk, causal, kv_lens, q_lens, seg_lens)
@@ -966,7 +1000,7 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
 
 def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbias=None, dbias_atomic=False,
                   dropout_p=0.0, seed=0, seed_dev=None, kv_lens=None, q_lens=None, seg_lens=None, max_seqlen=None,
-                  seg_offsets=None, bias=None, bias_grad=None):
+                  seg_offsets=None, bias=None, bias_grad=None, window=None):
     """Flash-attention backward into dq / dk / dv; returns the path that ran
     (1: the one-pass kernel, 0: the dQ and dK/dV kernels).  ``dropout_p``,
     ``seed``, ``seed_dev``: those of the forward call that produced ``o``
@@ -999,28 +1033,37 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
     ``attention_fwd``) dk / dv must be [B, Sk, Hkv, D]; each is the sum over
     its group's query heads, accumulated in fp32 inside the dK/dV kernel and
     rounded to bf16 once.  Always path 0; excludes ``dbias`` and everything
-    the forward excludes."""
+    the forward excludes.
+
+    ``window``: the forward call's sliding window (always path 0, no
+    ``dbias`` or ``bias_grad``); the dK/dV kernel ends a key block's query
+    loop at the last query that sees it.  Two calls give equal bits."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
+    W = _attn_window(window, causal, Sk, dropout_p, kv_lens, q_lens, seg_lens, bias, dbias, bias_grad)
     gview = _attn_bias_grad(bias_grad, bias, q, k, Sq, Sk)
     Hkv = _attn_gqa(q, k, v, dropout_p, kv_lens, q_lens, seg_lens, bias, dbias)
-    if Hkv:
-        if k.shape != (B, Sk, Hkv, D) or v.shape != (B, Sk, Hkv, D):
+    if Hkv or W:
+        Hk = Hkv or H
+        if k.shape != (B, Sk, Hk, D) or v.shape != (B, Sk, Hk, D):
             raise ValueError("attention: q/k/v shape mismatch")
         for name, t, shp in (("o", o, (B, Sq, H, D)), ("do", do, (B, Sq, H, D)), ("dq", dq, (B, Sq, H, D)),
-                             ("dk", dk, (B, Sk, Hkv, D)), ("dv", dv, (B, Sk, Hkv, D))):
+                             ("dk", dk, (B, Sk, Hk, D)), ("dv", dv, (B, Sk, Hk, D))):
             if tuple(t.shape) != shp:
                 raise ValueError(f"attention_bwd: {name} has shape {tuple(t.shape)}, expected {shp}"
                                  + (f" (grouped-query: dk / dv take the Hkv = {Hkv} K / V heads)"
-                                    if name in ("dk", "dv") else ""))
+                                    if Hkv and name in ("dk", "dv") else ""))
         if lse.shape != (B, H, Sq) or lse.dtype != torch.float32 or not lse.is_contiguous():
             raise ValueError("attention_bwd: bad lse")
         delta = torch.empty(B, H, Sq, device=q.device, dtype=torch.float32)
         sc = float(scale) if scale is not None else 1.0 / math.sqrt(D)
         path = ext().attention_bwd(_view4(q), _view4(k), _view4(v), _view4(o), _view4(do), _view4(dq), _view4(dk),
                                    _view4(dv), lse.data_ptr(), delta.data_ptr(), B, H, Sq, Sk, D, sc, bool(causal),
-                                   _stream(), kv_heads=Hkv)
-        STATS["attention_gqa"] += 1
+                                   _stream(), kv_heads=Hkv, **({"window": W} if W else {}))
+        if Hkv:
+            STATS["attention_gqa"] += 1
+        if W:
+            STATS["attention_window"] += 1
         STATS["attention_bwd"] += 1
         return path
     bview, bkeep = _attn_bias(bias, q, Sq, Sk, causal, kv_lens, q_lens, seg_lens, dbias)

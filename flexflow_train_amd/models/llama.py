@@ -32,6 +32,9 @@ class LlamaConfig:
     # the MLP's gate as one SWIGLU node (silu(gate) * up) instead of the
     # multiply(multiply(gate, sigmoid(gate)), up) chain
     swiglu_op: bool = False
+    # sliding-window causal attention in every layer: a query sees the
+    # sliding_window most recent positions, its own included (0: global)
+    sliding_window: int = 0
 
     @property
     def head_dim(self) -> int:
@@ -60,7 +63,8 @@ def build_llama(model: FFModel, cfg: LlamaConfig) -> Tuple[Dict[str, object], ob
         q = model.rope(q, cfg.rope_theta, seq_dim=1, name=f"{p}.q_rope")
         k = model.rope(k, cfg.rope_theta, seq_dim=1, name=f"{p}.k_rope")
         q, k, v = (model.transpose(t, [0, 2, 1, 3], name=f"{p}.{n}_t") for t, n in ((q, "q"), (k, "k"), (v, "v")))
-        a = model.scaled_dot_product_attention(q, k, v, causal=True, name=f"{p}.attn")
+        a = model.scaled_dot_product_attention(q, k, v, causal=True, name=f"{p}.attn",
+                                               window=cfg.sliding_window or None)
         a = model.reshape(model.transpose(a, [0, 2, 1, 3], name=f"{p}.attn_t"), [B, S, E], name=f"{p}.attn_merge")
         x = model.add(x, dense(a, E, f"{p}.o_proj"), name=f"{p}.attn_residual")
         h = model.rms_norm(x, cfg.rms_norm_eps, name=f"{p}.post_attn_norm")

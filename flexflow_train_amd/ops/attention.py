@@ -155,10 +155,11 @@ def _torch_packed_attention(q, k, v, causal, scale, seg_lens, max_seqlen=None, d
     return o.transpose(1, 2).to(q.dtype)
 
 
-def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=None, bias=None):
+def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=None, bias=None, window=0):
     # q,k,v: [B, S, H, D] -> [B, S, H, D]; drop = (keep mask [B, H, Sq, Sk], keep scale)
     # kv_lens, q_lens: [B] integer key / query lengths (module docstring)
     # bias: additive float mask broadcastable to [B, H, Sq, Sk]; a row with every key at -inf gives zeros
+    # window (with causal): key k is visible to query q iff 0 <= q - k < window; 0 = none
     qt, kt, vt = (t.transpose(1, 2) for t in (q, k, v))
     dead = qdead = None
     if q_lens is not None:
@@ -182,6 +183,8 @@ def _torch_attention(q, k, v, causal, scale, drop=None, kv_lens=None, q_lens=Non
     if causal:
         Sq, Sk = s.shape[-2:]
         mask = torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).triu(1)
+        if window:
+            mask |= torch.ones(Sq, Sk, dtype=torch.bool, device=s.device).tril(-int(window))
         s = s.masked_fill(mask, float("-inf"))
     rowdead = None
     if bias is not None:
@@ -661,7 +664,13 @@ class ScaledDotProductAttentionOp(OpImpl):
     existing kernels run as for Hkv == H, and dk / dv are reduced over the
     group in fp32 and cast once.  Everything else runs _torch_attention on
     K / V expanded inside the autograd graph.  The dropout mask and the
-    fallback's mask keep H as their head count."""
+    fallback's mask keep H as their head count.
+
+    Sliding-window causal attention: attribute ``window`` = W >= 1 (absent or
+    0: none; needs ``causal``): key k is visible to query q iff 0 <= q - k < W.
+    The flash case without dropout runs the WINDOW kernels, in place on the
+    Hkv-head K / V; with dropout, and everywhere else, _torch_attention adds
+    the band to its causal mask."""
 
     def forward(self, ctx: OpContext, inputs, weights):
         q, k, v = inputs[:3]
@@ -683,6 +692,9 @@ class ScaledDotProductAttentionOp(OpImpl):
             raise ValueError(f"{ctx.name}: causal cannot be combined with a mask")
         if causal and Sq != Sk:
             raise ValueError(f"{ctx.name}: causal needs Sq == Sk")
+        window = int(ctx.a("window", 0) or 0)
+        if window < 0 or (window and not causal):
+            raise ValueError(f"{ctx.name}: window must be >= 1 and needs causal")
         scale = float(ctx.a("scale", 0.0) or 0.0) or 1.0 / math.sqrt(D)
         # the mask as it came in: what its gradient is shaped and typed like (a bool mask gets none)
         mask_in = None if mask is None or mask.dtype == torch.bool else (tuple(mask.shape), mask.dtype)
@@ -704,7 +716,8 @@ class ScaledDotProductAttentionOp(OpImpl):
             drop = (p_drop, _drop_seed(ctx), _drop_step(ctx, q.device))
         use_flash = (q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == q.dtype and v.dtype == q.dtype
                      and D in (64, 128) and v.shape[3] == D and K.available()
-                     and (mask is None or _flash_bias_ok(mask, Sk)))
+                     and (mask is None or _flash_bias_ok(mask, Sk))
+                     and not (window and drop))   # the WINDOW kernels have no dropout form
         if use_flash:
             q, k, v = (t if t.stride(3) == 1 and t.is_contiguous() else t.contiguous() for t in (q, k, v))
             if G > 1 and (mask is not None or drop):
@@ -713,17 +726,20 @@ class ScaledDotProductAttentionOp(OpImpl):
                 k, v = k.repeat_interleave(G, dim=1), v.repeat_interleave(G, dim=1)
             o = torch.empty(B, H, Sq, D, device=q.device, dtype=q.dtype)
             kw = dict(dropout_p=drop[0], seed=drop[1], seed_dev=drop[2]) if drop else {}
+            if window:
+                kw["window"] = window
             _, lse = K.attention_fwd(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2), causal=causal,
                                      scale=scale, out=o.transpose(1, 2), bias=mask, **kw)
         else:
             o = _torch_attention(q.transpose(1, 2), _expand_kv(k, G).transpose(1, 2),
                                  _expand_kv(v, G).transpose(1, 2), causal, scale,
-                                 _fallback_mask(drop, B, H, Sq, Sk), bias=mask).transpose(1, 2).contiguous()
+                                 _fallback_mask(drop, B, H, Sq, Sk), bias=mask,
+                                 window=window).transpose(1, 2).contiguous()
             lse = None
-        return [o], (q, k, v, mask, o, lse, causal, scale, drop, Hkv, mask_in)
+        return [o], (q, k, v, mask, o, lse, (causal, window), scale, drop, Hkv, mask_in)
 
     def backward(self, ctx, saved, grad_outputs, weight_grads, need_input_grad):
-        q, k, v, mask, o, lse, causal, scale, drop, Hkv, mask_in = saved
+        q, k, v, mask, o, lse, (causal, window), scale, drop, Hkv, mask_in = saved
         B, H, Sq, D = q.shape
         Sk = k.shape[2]
         G = H // Hkv
@@ -743,6 +759,8 @@ class ScaledDotProductAttentionOp(OpImpl):
                 # written by the flash dbias kernel, summed there over a batch / head axis of extent 1
                 dmask = torch.empty(mask.shape[0], mask.shape[1], Sq, Sk, device=q.device, dtype=torch.float32)
                 kw["bias_grad"] = dmask
+            if window:
+                kw["window"] = window
             t = lambda x: x.transpose(1, 2)
             K.attention_bwd(t(q), t(k), t(v), t(o), lse, t(do), t(dq), t(dk), t(dv), causal=causal, scale=scale,
                             bias=mask, **kw)
@@ -758,7 +776,7 @@ class ScaledDotProductAttentionOp(OpImpl):
             # K / V expanded inside the graph: autograd does the group sum
             ref = _torch_attention(qf.transpose(1, 2), _expand_kv(kf, G).transpose(1, 2),
                                    _expand_kv(vf, G).transpose(1, 2), causal, scale,
-                                   _fallback_mask(drop, B, H, Sq, Sk), bias=mf)
+                                   _fallback_mask(drop, B, H, Sq, Sk), bias=mf, window=window)
             ref.float().backward(do.float().transpose(1, 2))
             dq, dk, dv = (x.grad.to(do.dtype) for x in (qf, kf, vf))
             if want_db:

@@ -16,6 +16,8 @@ two builds: FF_PKG_ROOT=ab_prev python tools/attn_time.py).
                                                                        the SDPA node against the unfused chain)
     python tools/attn_time.py --gqa G                                 (grouped-query K / V heads, H / G of them,
                                                                        against the expanded call and the H-head call)
+    python tools/attn_time.py --window W                              (sliding-window causal attention at S = 8192
+                                                                       against global causal and a dense band mask)
 
 --d128 appends two D = 128 shapes to whichever mode is run.
 """
@@ -485,8 +487,89 @@ def gqa_ab(G, iters, rounds=5):
         print(json.dumps(rec), flush=True)
 
 
+def window_ab(W, iters, rounds=5):
+    """Interleaved same-process timing of sliding-window causal attention at
+    S = 8192, B = 2, H = 32 query heads over 8 K / V heads, D in {128, 64}:
+      window  the WINDOW kernels, in place on the 8-head K / V;
+      causal  the same call without a window (global causal attention);
+      band    what a caller had to do before: a dense [1, 1, S, S] additive band
+              mask through the BIAS kernels on K / V expanded to H heads (the
+              expansion and the group sum of dK / dV are not timed).
+    `fwd_tiles_window_over_causal`: (query block, key tile) pairs the forward
+    walks with the window over those of the causal call."""
+    import statistics
+    B, S, H, Hkv = 2, 8192, 32, 8
+    for D in (128, 64):
+        g = torch.Generator(device="cuda").manual_seed(0)
+        q, do = (torch.randn(B, S, H, D, device="cuda", dtype=torch.bfloat16, generator=g) for _ in range(2))
+        k, v = (torch.randn(B, S, Hkv, D, device="cuda", dtype=torch.bfloat16, generator=g) for _ in range(2))
+        ke, ve = k.repeat_interleave(H // Hkv, dim=2), v.repeat_interleave(H // Hkv, dim=2)
+        dq, dk, dv, dke, dve = (torch.empty_like(x) for x in (q, k, v, ke, ve))
+        o = torch.empty_like(q)
+        d = torch.arange(S, device="cuda").view(S, 1) - torch.arange(S, device="cuda").view(1, S)
+        band = torch.zeros(1, 1, S, S, device="cuda").masked_fill_(((d < 0) | (d >= W)).view(1, 1, S, S), float("-inf"))
+        del d
+        calls = {"window": ((q, k, v), (dq, dk, dv), dict(causal=True, window=W)),
+                 "causal": ((q, k, v), (dq, dk, dv), dict(causal=True)),
+                 "band": ((q, ke, ve), (dq, dke, dve), dict(bias=band))}
+        t = {}
+        for _ in range(rounds):
+            for tag, (ins, outs, kw) in calls.items():
+                _, lse = K.attention_fwd(*ins, out=o, **kw)
+                t.setdefault(("fwd", tag), []).append(_time(lambda: K.attention_fwd(*ins, out=o, **kw), iters))
+                t.setdefault(("bwd", tag), []).append(_time(lambda: K.attention_bwd(*ins, o, lse, do, *outs, **kw), iters))
+        med = {key: statistics.median(x) for key, x in t.items()}
+        tiles = lambda w: sum((qb + 128 + 63) // 64 - max(qb - w + 1, 0) // 64 for qb in range(0, S, 128))  # noqa: E731
+        rec = {"S": S, "B": B, "H": H, "Hkv": Hkv, "D": D, "window": W, "iters": iters, "rounds": rounds,
+               "fwd_tiles_window_over_causal": round(tiles(W) / tiles(S), 4), "two_w_over_s": round(2 * W / S, 4)}
+        for which in ("fwd", "bwd"):
+            for tag in calls:
+                xs = t[(which, tag)]
+                rec[f"{which}_ms_{tag}"] = round(med[(which, tag)], 4)
+                rec[f"{which}_spread_{tag}"] = round((max(xs) - min(xs)) / med[(which, tag)], 4)
+            rec[f"{which}_window_over_causal"] = round(med[(which, "window")] / med[(which, "causal")], 3)
+            rec[f"{which}_window_over_band"] = round(med[(which, "window")] / med[(which, "band")], 3)
+        print(json.dumps(rec), flush=True)
+
+
+def window_llama(W, iters=10, rounds=5):
+    """The build_llama training step (8 layers x 1024, S = 2048, B = 4, 16
+    query heads over 4 K / V heads) with sliding_window in {0, W}, interleaved."""
+    import statistics
+
+    import numpy as np
+
+    from flexflow_train_amd.core import AdamOptimizer, FFConfig, FFModel, LossType
+    from flexflow_train_amd.models.llama import LlamaConfig, build_llama, llama_synthetic
+
+    steps = {}
+    for w in (0, W):
+        lc = LlamaConfig(vocab_size=32000, hidden_size=1024, num_layers=8, num_heads=16, num_kv_heads=4,
+                         intermediate_size=2816, sequence_length=2048, batch_size=4, sliding_window=w)
+        m = FFModel(FFConfig())
+        build_llama(m, lc)
+        m.compile(optimizer=AdamOptimizer(m, alpha=1e-4), loss_type=LossType.LOSS_SPARSE_CATEGORICAL_CROSSENTROPY)
+        ex = m.executor
+        feeds, labels = llama_synthetic(lc, np.random.default_rng(0))
+        feeds = {n: torch.from_numpy(x).to(ex.cfg.device) for n, x in feeds.items()}
+        labels = torch.from_numpy(labels).to(ex.cfg.device)
+        steps[w] = (lambda ex=ex, feeds=feeds, labels=labels: ex.train_step(feeds, labels))
+    t = {w: [] for w in steps}
+    for _ in range(rounds):
+        for w, fn in steps.items():
+            t[w].append(_time(fn, iters))
+    print(json.dumps({"llama_step": "8x1024 S=2048 B=4", "iters": iters, "rounds": rounds,
+                      **{f"ms_window_{w}": round(statistics.median(x), 3) for w, x in t.items()},
+                      **{f"rounds_window_{w}": [round(y, 3) for y in x] for w, x in t.items()},
+                      "attention_window_calls": K.STATS["attention_window"]}), flush=True)
+
+
 def main():
-    if "--gqa" in sys.argv:            # grouped-query K / V heads against the expanded and the H-head call
+    if "--window-llama" in sys.argv:   # the LLaMA step with and without sliding_window
+        return window_llama(int(sys.argv[sys.argv.index("--window-llama") + 1]))
+    if "--window" in sys.argv:        # sliding-window causal attention against global causal and the dense band mask
+        return window_ab(int(sys.argv[sys.argv.index("--window") + 1]), 10)
+    if "--gqa" in sys.argv:           # grouped-query K / V heads against the expanded and the H-head call
         return gqa_ab(int(sys.argv[sys.argv.index("--gqa") + 1]), 200)
     if "--bias-grad" in sys.argv:      # gradient of a learned bias: the extra launch, and SDPA against the unfused chain
         return bias_grad_ab(30)
