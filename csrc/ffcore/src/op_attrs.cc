@@ -1495,6 +1495,9 @@ OpSpec fused_parallel_spec() {
 // Inputs: x [B, D], expert ids [B, k] (int), gate weights [B, k].
 // Weights: w1 [E, D, H], b1 [E, H], w2 [E, H, O], b2 [E, O].
 // out[b] = sum_j gate[b, j] * expert_{id[b, j]}(x[b]).
+// activation "swiglu" (gated experts): w1 is [E, D, 2H], gate projection in
+// columns 0 .. H-1 and up projection in H .. 2H-1, expert(x) = (silu(g) * u) W2
+// with [g | u] = x W1; no biases.
 // Expert parallelism, two lowerings:
 //  * "replicated": token inputs carry discard_copy c; experts are sharded c
 //    ways; each rank applies only its experts -> output sum_degree c
@@ -1517,11 +1520,15 @@ OpSpec experts_spec() {
     require(nd(in[1]) == 2 && nd(in[2]) == 2, a, "expert ids / gates must be [batch, k]");
     require(in[1].dims == in[2].dims && in[1].dims[0] == in[0].dims[0], a, "ids / gates / x batch mismatch");
     require(in[1].dims[1] <= a.i("num_experts"), a, "k exceeds the number of experts");
+    require(!(a.s("activation") == "swiglu" && a.b("use_bias")), a,
+            "activation 'swiglu' takes no biases: use_bias=True is refused");
     return Shapes{TensorShape{{in[0].dims[0], a.i("out_dim")}, in[0].dtype}};
   };
   s.wts = [](const OpAttrs& a, const Shapes& in) {
     const int64_t E = a.i("num_experts"), D = in[0].dims[1], H = a.i("hidden_size"), O = a.i("out_dim");
-    Shapes w{TensorShape{{E, D, H}, in[0].dtype}};
+    const bool gated = a.s("activation") == "swiglu";
+    require(!(gated && a.b("use_bias")), a, "activation 'swiglu' takes no biases: use_bias=True is refused");
+    Shapes w{TensorShape{{E, D, gated ? 2 * H : H}, in[0].dtype}};
     if (a.b("use_bias")) w.push_back(TensorShape{{E, H}, in[0].dtype});
     w.push_back(TensorShape{{E, H, O}, in[0].dtype});
     if (a.b("use_bias")) w.push_back(TensorShape{{E, O}, in[0].dtype});
@@ -1780,8 +1787,9 @@ OpWork estimate_op_work(const OpAttrs& a, const std::vector<TensorShape>& in,
       const double E = static_cast<double>(a.i("num_experts")), El = static_cast<double>(w[0].dims[0]);
       const double D = static_cast<double>(in[0].dims[1]), H = static_cast<double>(a.i("hidden_size"));
       const double O = static_cast<double>(a.i("out_dim"));
-      r.flops = 2 * pairs * (El / E) * (D * H + H * O);
-      r.bytes = static_cast<double>(w[0].size_bytes()) * (1 + (O / D)) + 4 * pairs * (D + O);
+      const bool gated = a.s("activation") == "swiglu";   // w1 is [E, D, 2H]
+      r.flops = 2 * pairs * (El / E) * ((gated ? 2 : 1) * D * H + H * O);
+      r.bytes = static_cast<double>(w[0].size_bytes()) * (1 + (O / D) / (gated ? 2 : 1)) + 4 * pairs * (D + O);
       r.matmul_like = true;
       r.mfma_efficiency_hint = std::min(1.0, pairs * (El / E) / El / 512.0 + 0.2);
       break;

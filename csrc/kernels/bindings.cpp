@@ -368,6 +368,20 @@ PYBIND11_MODULE(_ffkernels, m) {
     p.sB = sB; p.sC = sC; p.sBias = sBias; p.act = act; p.act_bwd = act_bwd; p.beta = beta; p.out_f32 = out_f32;
     grouped_gemm_bf16(p, S(st));
   });
+  m.def("grouped_gemm_swiglu", [](uintptr_t xs, uintptr_t w1, uintptr_t gu, uintptr_t h, uintptr_t offsets,
+                                  uintptr_t tile_group, uintptr_t tile_row0, uintptr_t n_tiles, int El, int T, int D,
+                                  int H, uintptr_t st) {
+    auto I = [](uintptr_t p) { return reinterpret_cast<const int*>(p); };
+    grouped_gemm_swiglu(P(xs), P(w1), P(gu), P(h), I(offsets), I(tile_group), I(tile_row0), I(n_tiles), El, T, D, H,
+                        S(st));
+  });
+  m.def("grouped_gemm_swiglu_bwd", [](uintptr_t dy, uintptr_t w2, uintptr_t gu, uintptr_t dgu, uintptr_t offsets,
+                                      uintptr_t tile_group, uintptr_t tile_row0, uintptr_t n_tiles, int El, int T,
+                                      int O, int H, uintptr_t st) {
+    auto I = [](uintptr_t p) { return reinterpret_cast<const int*>(p); };
+    grouped_gemm_swiglu_bwd(P(dy), P(w2), P(gu), P(dgu), I(offsets), I(tile_group), I(tile_row0), I(n_tiles), El, T, O,
+                            H, S(st));
+  });
   m.def("moe_route_ws", &moe_route_ws);
   m.def("moe_route", [](uintptr_t ids, int64_t Pn, int e0, int El, uintptr_t offsets, uintptr_t perm, uintptr_t pos,
                         uintptr_t tile_group, uintptr_t tile_row0, uintptr_t n_tiles, int T, uintptr_t ws,

@@ -355,6 +355,21 @@ void moe_dgate(const void* dout, const void* y, const int* pos, float* dgate, in
 // out[e] = column sums of x[offsets[e] : offsets[e+1]] (fp32, fixed order); N % 8 == 0
 void moe_segment_colsum(const void* x, const int* offsets, float* out, int El, int N, hipStream_t st);
 
+// ---- moe_swiglu.hip: gated (SwiGLU) experts over moe_route's row-tile map (T
+// = its static size).  bf16, contiguous, 16-byte aligned; D, H, O multiples of
+// 8; 1 <= El <= MOE_MAX_LOCAL_EXPERTS.  Rows at or beyond a group's end (and so
+// at or beyond offsets[El]) are never written.
+constexpr int MOE_MAX_LOCAL_EXPERTS = 256;
+// [g | u] = xs[rows_e] W1[e] with W1 [El, D, 2H] (gate columns, then up columns):
+// gu [P, 2H] receives g | u, h [P, H] receives silu(g) * u from the fp32 accumulators
+void grouped_gemm_swiglu(const void* xs, const void* w1, void* gu, void* h, const int* offsets, const int* tile_group,
+                         const int* tile_row0, const int* n_tiles, int El, int T, int D, int H, hipStream_t st);
+// dh = dy[rows_e] W2[e]^T with W2 [El, H, O], not stored: dgu [P, 2H] receives dg | du of
+// h = silu(g) * u at the saved gu [P, 2H]
+void grouped_gemm_swiglu_bwd(const void* dy, const void* w2, const void* gu, void* dgu, const int* offsets,
+                             const int* tile_group, const int* tile_row0, const int* n_tiles, int El, int T, int O,
+                             int H, hipStream_t st);
+
 // ---- tensorops.hip: general tensor operators (N-d, <= 6 dims)
 struct NdShape {
   int nd = 0;

@@ -28,20 +28,11 @@
 // K-tile, bijective XCD remap + grouped raster: as gemm.hip.
 #include "kernels.h"
 #include "mfma.h"
+#include "swiglu_math.h"   // swiglu_sigmoid / swiglu_y / swiglu_grad
 
 namespace ffk {
 
 namespace {
-
-// ---- the formulas, fp32, one definition each.  exp(-g) overflowing to inf
-// gives s = 0 and silu = g * 0 = -0; s is always finite, so no inf * 0 arises.
-__device__ __forceinline__ float swiglu_sigmoid(float g) { return 1.f / (1.f + expf(-g)); }
-__device__ __forceinline__ float swiglu_y(float g, float u) { return g * swiglu_sigmoid(g) * u; }
-__device__ __forceinline__ void swiglu_grad(float dy, float g, float u, float& dg, float& du) {
-  const float s = swiglu_sigmoid(g);
-  dg = dy * u * s * (1.f + g * (1.f - s));
-  du = dy * g * s;
-}
 
 // 8 consecutive elements as fp32: one 16-byte access for bf16, two for fp32
 template <class T>

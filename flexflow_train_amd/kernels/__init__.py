@@ -1719,6 +1719,114 @@ def grouped_gemm(a, b, route: MoeRouting, form: str = "nn", bias=None, act: str 
     return out
 
 
+# Gated (SwiGLU) experts (csrc/kernels/moe_swiglu.hip): w1 [El, D, 2H] holds the
+# gate projection in columns 0 .. H-1 and the up projection in H .. 2H-1.
+def _grouped_swiglu_dims(who: str, a, w, route: MoeRouting, gated_w: bool):
+    """Rule checks of both gated kernels; (El, K, H).  ``w`` is w1 [El, D, 2H]
+    (gated_w) or w2 [El, H, O]; ``a`` is [P, K] with K = D or O."""
+    if a.dim() != 2 or w.dim() != 3:
+        raise ValueError(f"{who}: a [P, K], weight [El, ., .]")
+    El, Kd = int(w.shape[0]), int(a.shape[1])
+    if gated_w:
+        if w.shape[2] % 2:
+            raise ValueError(f"{who}: w1 must be [El, D, 2H] (gate | up), got width {int(w.shape[2])}")
+        H, wk = int(w.shape[2]) // 2, int(w.shape[1])
+    else:
+        H, wk = int(w.shape[1]), int(w.shape[2])
+    if wk != Kd:
+        raise ValueError(f"{who}: inner dims differ ({Kd} vs {wk})")
+    if H <= 0 or Kd <= 0 or H % 8 or Kd % 8:
+        raise ValueError(f"{who}: H ({H}) and the contraction length ({Kd}) must be positive multiples of 8")
+    if not 1 <= El <= MOE_MAX_LOCAL_EXPERTS or El != route.num_local:
+        raise ValueError(f"{who}: the weight must hold one matrix per local expert (1 .. {MOE_MAX_LOCAL_EXPERTS})")
+    if a.shape[0] != route.pairs:
+        raise ValueError(f"{who}: a must have one row per routed pair")
+    if a.dtype != torch.bfloat16 or w.dtype != torch.bfloat16:
+        raise ValueError(f"{who}: operands are bf16")
+    return El, Kd, H
+
+
+def grouped_gemm_swiglu_reference(a, w1, route: MoeRouting, gu=None, h=None):
+    """Per-group torch products with the kernel's rounding points: g | u from
+    fp32 accumulation rounded to bf16, h = silu(g) * u from the fp32 values
+    rounded once; rows beyond the local pairs of given outputs stay."""
+    H = w1.shape[2] // 2
+    gu = torch.zeros(a.shape[0], 2 * H, dtype=a.dtype, device=a.device) if gu is None else gu
+    h = torch.zeros(a.shape[0], H, dtype=a.dtype, device=a.device) if h is None else h
+    off = route.offsets.tolist()
+    for e in range(route.num_local):
+        lo, hi = off[e], off[e + 1]
+        if hi > lo:
+            r = a[lo:hi].float() @ w1[e].float()
+            gu[lo:hi] = r.to(gu.dtype)
+            h[lo:hi] = (torch.nn.functional.silu(r[:, :H]) * r[:, H:]).to(h.dtype)
+    return gu, h
+
+
+def grouped_gemm_swiglu(a, w1, route: MoeRouting, gu=None, h=None):
+    """One launch over the expert row blocks of ``route``: gu[rows_e] = a[rows_e]
+    @ w1[e] (g | u, bf16, kept for the backward) and h = silu(g) * u from the
+    fp32 accumulators, rounded once.  a [P, D], w1 [El, D, 2H]; returns (gu
+    [P, 2H], h [P, H]); rows beyond the local pairs are never written."""
+    El, D, H = _grouped_swiglu_dims("grouped_gemm_swiglu", a, w1, route, True)
+    P = route.pairs
+    for t, name, n in ((gu, "gu", 2 * H), (h, "h", H)):
+        if t is not None and (tuple(t.shape) != (P, n) or t.dtype != torch.bfloat16):
+            raise ValueError(f"grouped_gemm_swiglu: {name} must be bf16 [P, {n}]")
+    if not a.is_cuda:
+        return grouped_gemm_swiglu_reference(a, w1, route, gu, h)
+    _check(a, "a", torch.bfloat16)
+    _check(w1, "w1", torch.bfloat16)
+    gu = torch.empty(P, 2 * H, dtype=torch.bfloat16, device=a.device) if gu is None else gu
+    h = torch.empty(P, H, dtype=torch.bfloat16, device=a.device) if h is None else h
+    _check(gu, "gu", torch.bfloat16)
+    _check(h, "h", torch.bfloat16)
+    ext().grouped_gemm_swiglu(_p(a), _p(w1), _p(gu), _p(h), _p(route.offsets), _p(route.tile_group),
+                              _p(route.tile_row0), _p(route.n_tiles), El, route.tile_group.numel(), D, H, _stream())
+    STATS["grouped_gemm_swiglu"] += 1
+    return gu, h
+
+
+def grouped_gemm_swiglu_bwd_reference(dy, w2, route: MoeRouting, gu, out=None):
+    H = w2.shape[1]
+    out = torch.zeros_like(gu) if out is None else out
+    off = route.offsets.tolist()
+    for e in range(route.num_local):
+        lo, hi = off[e], off[e + 1]
+        if hi > lo:
+            dh = dy[lo:hi].float() @ w2[e].float().t()
+            g, u = gu[lo:hi, :H].float(), gu[lo:hi, H:].float()
+            s = torch.sigmoid(g)
+            out[lo:hi, :H] = (dh * u * s * (1 + g * (1 - s))).to(out.dtype)
+            out[lo:hi, H:] = (dh * g * s).to(out.dtype)
+    return out
+
+
+def grouped_gemm_swiglu_bwd(dy, w2, route: MoeRouting, gu, out=None):
+    """dgu [P, 2H] = dg | du of h = silu(g) * u for dh = dy[rows_e] @ w2[e]^T,
+    which is never stored: the product's epilogue reads g, u from the saved
+    ``gu`` [P, 2H].  dy [P, O], w2 [El, H, O]; one launch."""
+    El, O, H = _grouped_swiglu_dims("grouped_gemm_swiglu_bwd", dy, w2, route, False)
+    P = route.pairs
+    for t, name in ((gu, "gu"), (out, "out")):
+        if t is not None and (tuple(t.shape) != (P, 2 * H) or t.dtype != torch.bfloat16):
+            raise ValueError(f"grouped_gemm_swiglu_bwd: {name} must be bf16 [P, {2 * H}]")
+    if gu is None:
+        raise ValueError("grouped_gemm_swiglu_bwd: gu is required")
+    if not dy.is_cuda:
+        return grouped_gemm_swiglu_bwd_reference(dy, w2, route, gu, out)
+    _check(dy, "dy", torch.bfloat16)
+    _check(w2, "w2", torch.bfloat16)
+    _check(gu, "gu", torch.bfloat16)
+    out = torch.empty(P, 2 * H, dtype=torch.bfloat16, device=dy.device) if out is None else out
+    _check(out, "out", torch.bfloat16)
+    ext().grouped_gemm_swiglu_bwd(_p(dy), _p(w2), _p(gu), _p(out), _p(route.offsets), _p(route.tile_group),
+                                  _p(route.tile_row0), _p(route.n_tiles), El, route.tile_group.numel(), O, H,
+                                  _stream())
+    STATS["grouped_gemm_swiglu_bwd"] += 1
+    return out
+
+
 # ---------------------------------------------------------------------------
 # General tensor operators (csrc/kernels/tensorops.hip).  Inputs: contiguous
 # GPU tensors in bf16 or fp32; _check's 16-byte alignment is not required.

@@ -3,7 +3,9 @@
 Pre-norm blocks of RMS norm, bias-free q / k / v projections, rotary position
 embeddings on q and k, causal grouped-query attention (``SDPA``), and a SwiGLU
 MLP (SiLU spelled multiply(gate, sigmoid(gate))); a final RMS norm, the LM
-head and a softmax.  No learned positions and no biases anywhere.
+head and a softmax.  No learned positions and no biases anywhere.  With
+``num_experts > 0`` the MLP is a routed mixture of SwiGLU experts (``EXPERTS``
+with ``activation="swiglu"``).
 """
 from __future__ import annotations
 
@@ -35,6 +37,11 @@ class LlamaConfig:
     # sliding-window causal attention in every layer: a query sees the
     # sliding_window most recent positions, its own included (0: global)
     sliding_window: int = 0
+    # num_experts > 0: every layer's MLP is a mixture of gated (SwiGLU) experts
+    # of intermediate_size behind a bias-free softmax router with top-k
+    # selection (Mixtral style); 0: the dense MLP
+    num_experts: int = 0
+    experts_per_token: int = 2
 
     @property
     def head_dim(self) -> int:
@@ -68,6 +75,14 @@ def build_llama(model: FFModel, cfg: LlamaConfig) -> Tuple[Dict[str, object], ob
         a = model.reshape(model.transpose(a, [0, 2, 1, 3], name=f"{p}.attn_t"), [B, S, E], name=f"{p}.attn_merge")
         x = model.add(x, dense(a, E, f"{p}.o_proj"), name=f"{p}.attn_residual")
         h = model.rms_norm(x, cfg.rms_norm_eps, name=f"{p}.post_attn_norm")
+        if cfg.num_experts > 0:
+            t = model.reshape(h, [B * S, E], name=f"{p}.moe_tokens")
+            router = model.softmax(dense(t, cfg.num_experts, f"{p}.router"), -1, name=f"{p}.router_softmax")
+            vals, idx = model.top_k(router, cfg.experts_per_token, True, name=f"{p}.router_topk")
+            t = model.experts(t, idx, vals, cfg.num_experts, cfg.intermediate_size, out_dim=E, activation="swiglu",
+                              use_bias=False, name=f"{p}.experts")
+            x = model.add(x, model.reshape(t, [B, S, E], name=f"{p}.moe_merge"), name=f"{p}.mlp_residual")
+            continue
         gate = dense(h, cfg.intermediate_size, f"{p}.gate_proj")
         up = dense(h, cfg.intermediate_size, f"{p}.up_proj")
         if cfg.swiglu_op:

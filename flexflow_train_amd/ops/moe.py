@@ -8,6 +8,12 @@ expert block is one operator (IR: csrc/ffcore/src/op_attrs.cc experts_spec):
 
     out[b] = sum_j gate[b, j] * (W2[e] act(W1[e] x[b] + b1[e]) + b2[e]),  e = ids[b, j]
 
+Gated experts (``activation="swiglu"``, no biases; Mixtral / DeepSeek-MoE /
+Qwen-MoE style): ``w1`` is one tensor [E, D, 2H] whose columns 0 .. H-1 are
+the gate projection and H .. 2H-1 the up projection, and
+
+    out[b] = sum_j gate[b, j] * (h W2[e]),  h = silu(g) * u,  [g | u] = x[b] W1[e]
+
 Dropless routing: the (token, slot) pairs are sorted by expert, every expert
 runs two GEMMs over its contiguous row block, results are scaled by the gate
 and summed back into their tokens.
@@ -21,7 +27,15 @@ map) -> ``moe_gather_rows`` -> grouped NN with bias + activation + pre ->
 grouped NN with bias -> ``moe_combine``; backward: scaled gather and
 ``moe_dgate``, grouped TN (dW2), grouped NT with the activation gradient (du),
 grouped TN (dW1), grouped NT (dxs), unweighted combine (dx), per-expert column
-sums for the bias gradients (a fixed-order kernel, no atomics).  Buffers are
+sums for the bias gradients (a fixed-order kernel, no atomics).  Gated experts
+replace the first GEMM by ``grouped_gemm_swiglu`` (one launch: g | u and h
+from the fp32 accumulators) and the activation-gradient NT product by
+``grouped_gemm_swiglu_bwd`` (dh is never stored; dg | du come out of the
+epilogue); with the fused w1, dW1 is one grouped TN product with N = 2H and
+dxs one grouped NT product with K = 2H (csrc/kernels/moe_swiglu.hip).
+``FF_MOE_SWIGLU_FUSED=0`` composes the same path from the existing kernels
+(grouped NN with N = 2H + ``swiglu_fwd``; grouped NT + ``swiglu_bwd``), the
+A/B baseline.  Buffers are
 sized by the static pair count, nothing is read back and no loop runs over
 experts, so the step can be captured into a hipGraph
 (``Executor.make_graphed_train_step``).
@@ -64,6 +78,23 @@ _ACT = {"none": lambda t: t, "relu": torch.relu, "gelu": lambda t: torch.nn.func
         "sigmoid": torch.sigmoid, "tanh": torch.tanh}
 
 
+def _swiglu(gu):
+    """h = silu(g) * u of gu = [g | u], fp32 math on the stored g, u."""
+    H = gu.shape[1] // 2
+    return (torch.nn.functional.silu(gu[:, :H].float()) * gu[:, H:].float()).to(gu.dtype)
+
+
+_ACT["swiglu"] = _swiglu
+
+
+def _check_swiglu(w1, b1, w2, b2):
+    if b1 is not None or b2 is not None:
+        raise ValueError("EXPERTS: activation 'swiglu' takes no biases (use_bias=True is refused)")
+    if w1.shape[2] != 2 * w2.shape[1]:
+        raise ValueError(f"EXPERTS: activation 'swiglu' needs w1 [E, D, 2H] (gate | up) for w2 [E, H, O]; got w1 width "
+                         f"{int(w1.shape[2])} with H = {int(w2.shape[1])}")
+
+
 class ExpertGroup:
     """Ranks exchanging tokens in all-to-all expert parallelism (ordered by
     expert shard)."""
@@ -94,9 +125,9 @@ def _gpu_bf16(t) -> bool:
 def _expert_mlp_fwd(xs, eid, w1, b1, w2, b2, act, El):
     """Rows ``xs`` sorted by local expert id ``eid``; returns (y, pre, h, bounds)."""
     counts = torch.bincount(eid, minlength=El).tolist()
-    H, O = w1.shape[2], w2.shape[2]
-    pre = torch.empty(xs.shape[0], H, dtype=xs.dtype, device=xs.device)
-    h = torch.empty_like(pre)
+    O = w2.shape[2]
+    pre = torch.empty(xs.shape[0], w1.shape[2], dtype=xs.dtype, device=xs.device)   # swiglu: g | u, width 2H
+    h = torch.empty(xs.shape[0], w2.shape[1], dtype=xs.dtype, device=xs.device)
     y = torch.empty(xs.shape[0], O, dtype=xs.dtype, device=xs.device)
     lo = 0
     bounds = []
@@ -105,7 +136,11 @@ def _expert_mlp_fwd(xs, eid, w1, b1, w2, b2, act, El):
         bounds.append((lo, hi))
         if n:
             xe = xs[lo:hi]
-            if _gpu_bf16(xe):
+            if _gpu_bf16(xe) and act == "swiglu":
+                matmul(xe, w1[e], out=pre[lo:hi])
+                h[lo:hi] = _swiglu(pre[lo:hi])
+                y[lo:hi] = matmul(h[lo:hi], w2[e])
+            elif _gpu_bf16(xe):
                 h[lo:hi] = matmul(xe, w1[e], bias=b1[e] if b1 is not None else None, act=act,
                                   pre=pre[lo:hi] if act != "none" else None)
                 if act == "none":
@@ -171,15 +206,25 @@ def _use_grouped(x, ids, gate, w1, b1, w2, b2, act) -> bool:
     per expert and 0.20x at 256 (profiles/r7/moe_grouped.txt)."""
     if os.environ.get("FF_MOE_GROUPED", "1") == "0" or not (_gpu_bf16(x) and _gpu_bf16(gate) and ids.is_cuda):
         return False
-    if act not in ("none", "relu", "sigmoid", "tanh", "gelu") or x.dim() != 2:
+    if act not in ("none", "relu", "sigmoid", "tanh", "gelu", "swiglu") or x.dim() != 2:
         return False
     for t in (w1, w2, b1, b2):
         if t is not None and not (_gpu_bf16(t) and t.is_contiguous() and t.data_ptr() % 16 == 0):
             return False
     H, O = int(w1.shape[2]), int(w2.shape[2])
+    if act == "swiglu":
+        H //= 2   # _check_swiglu has run: no biases, w1 [E, D, 2H]; 2H % 8 is checked below, H % 8 here
+        if H % 8:
+            return False
     if w2.shape[0] != w1.shape[0] or w2.shape[1] != H or O % 8 or not K.grouped_gemm_supported(x.contiguous(), w1, "nn"):
         return False
     return True
+
+
+def _swiglu_fused() -> bool:
+    """Gated experts on the two kernels of moe_swiglu.hip (default) or, with
+    FF_MOE_SWIGLU_FUSED=0, composed from the existing grouped and SwiGLU kernels."""
+    return os.environ.get("FF_MOE_SWIGLU_FUSED", "1") != "0"
 
 
 def _tn_into(a, g, route, buf):
@@ -195,12 +240,20 @@ def _tn_into(a, g, route, buf):
 
 def _grouped_forward(ctx, x, ids, gate, w1, b1, w2, b2, act, El):
     """route -> gather -> grouped NN (bias + act + pre) -> grouped NN (bias)
-    -> combine; every size on the device, nothing read back."""
+    -> combine; every size on the device, nothing read back.  Gated experts:
+    the first GEMM is the dual-weight kernel and ``pre`` is gu = g | u."""
     x, gate = x.contiguous(), gate.contiguous()
     ids32 = ids.contiguous() if ids.dtype == torch.int32 else ids.to(torch.int32).contiguous()
     route = K.moe_route(ids32, ctx.sum_index * El, El)
     xs = K.moe_gather_rows(x, route)
-    if act != "none":
+    if act == "swiglu":
+        if _swiglu_fused():
+            pre, h = K.grouped_gemm_swiglu(xs, w1, route)
+        else:
+            H = w2.shape[1]
+            pre = K.grouped_gemm(xs, w1, route, "nn")
+            h = K.swiglu_fwd(pre[:, :H], pre[:, H:])
+    elif act != "none":
         pre = torch.empty(xs.shape[0], w1.shape[2], dtype=xs.dtype, device=xs.device)
         h = K.grouped_gemm(xs, w1, route, "nn", bias=b1, act=act, pre=pre)
     else:
@@ -220,7 +273,15 @@ def _grouped_backward(saved, act, grads, dout, need_dx, need_dgate):
     if db2 is not None:
         acc_grad(db2, K.moe_segment_colsum(dy, route))
     _tn_into(h, dy, route, dW2)
-    du = K.grouped_gemm(dy, w2, route, "nt", aux=pre if act != "none" else None, act=act)
+    if act == "swiglu":   # du = dg | du [P, 2H]
+        if _swiglu_fused():
+            du = K.grouped_gemm_swiglu_bwd(dy, w2, route, pre)
+        else:
+            H = w2.shape[1]
+            du = torch.empty_like(pre)
+            K.swiglu_bwd(K.grouped_gemm(dy, w2, route, "nt"), pre[:, :H], pre[:, H:], du[:, :H], du[:, H:])
+    else:
+        du = K.grouped_gemm(dy, w2, route, "nt", aux=pre if act != "none" else None, act=act)
     if db1 is not None:
         acc_grad(db1, K.moe_segment_colsum(du, route))
     _tn_into(xs, du, route, dW1)
@@ -243,6 +304,8 @@ class ExpertsOp(OpImpl):
         w1, b1, w2, b2 = self._weights(ctx, weights)
         act = ctx.a("activation", "relu")
         El = int(w1.shape[0])
+        if act == "swiglu":
+            _check_swiglu(w1, b1, w2, b2)
         grp: Optional[ExpertGroup] = ctx.extra.get("ep_group")
         if grp is None and _use_grouped(x, ids, gate, w1, b1, w2, b2, act):
             return _grouped_forward(ctx, x, ids, gate, w1, b1, w2, b2, act, El)

@@ -4,6 +4,10 @@ per-expert library-GEMM path (FF_MOE_GROUPED=0), one process, interleaved
 repetitions; then a whole MoE training step, hipGraph replay against eager.
 
     python tools/bench_moe.py [--tokens 8192] [--dim 1024] [--hidden 4096] [--experts 8 64] [--out FILE]
+
+``--activation swiglu``: the gated operator's forward + backward on the two kernels of moe_swiglu.hip against
+the path composed from the existing kernels (FF_MOE_SWIGLU_FUSED=0), and each kernel alone against what it
+replaces (grouped NN with N = 2H + swiglu_fwd; grouped NT + swiglu_bwd), interleaved in one process.
 """
 import argparse
 import json
@@ -80,6 +84,55 @@ def bench_operator(B, D, H, E, k, act, reps, iters, emit):
           "per_expert_launches": n0})
 
 
+def bench_swiglu(B, D, H, E, k, reps, iters, emit):
+    from flexflow_train_amd import kernels as K
+
+    g = torch.Generator().manual_seed(0)
+    rn = lambda *s: torch.randn(*s, generator=g).to(DEV, torch.bfloat16)  # noqa: E731
+    x, dout = rn(B, D), rn(B, D)
+    vals, ids = torch.topk(torch.softmax(torch.randn(B, E, generator=g), -1), k, -1)
+    ids, gate = ids.to(DEV, torch.int32), vals.to(DEV, torch.bfloat16)
+    ws = [rn(E, D, 2 * H) * 0.05, rn(E, H, D) * 0.05]
+    grads = [torch.zeros(w.shape, device=DEV, dtype=torch.float32) for w in ws]
+    impl = opbase.get_impl("EXPERTS")
+    ctx = opbase.OpContext(op_type="EXPERTS", attrs={"num_experts": E, "hidden_size": H, "out_dim": D,
+                                                      "activation": "swiglu", "use_bias": False}, name="moe")
+
+    def op(fused):
+        os.environ["FF_MOE_SWIGLU_FUSED"] = fused
+        outs, saved = impl.forward(ctx, [x, ids, gate], ws)
+        impl.backward(ctx, saved, [dout], grads, [True, False, True])
+
+    route = K.moe_route(ids, 0, E)
+    xs, dy = K.moe_gather_rows(x, route), K.moe_gather_rows(dout, route, scale=gate)
+    P = xs.shape[0]
+    gu, h, dgu = (torch.zeros(P, n, device=DEV, dtype=torch.bfloat16) for n in (2 * H, H, 2 * H))
+    dh = torch.zeros_like(h)
+    runs = {"op_fused": lambda: op("1"), "op_composed": lambda: op("0"),
+            "fwd_fused": lambda: K.grouped_gemm_swiglu(xs, ws[0], route, gu, h),
+            "fwd_composed": lambda: (K.grouped_gemm(xs, ws[0], route, "nn", out=gu),
+                                     K.swiglu_fwd(gu[:, :H], gu[:, H:], h)),
+            "bwd_fused": lambda: K.grouped_gemm_swiglu_bwd(dy, ws[1], route, gu, out=dgu),
+            "bwd_composed": lambda: (K.grouped_gemm(dy, ws[1], route, "nt", out=dh),
+                                     K.swiglu_bwd(dh, gu[:, :H], gu[:, H:], dgu[:, :H], dgu[:, H:]))}
+    times = {n: [] for n in runs}
+    for fn in runs.values():
+        fn()
+    for _ in range(reps):
+        for n, fn in runs.items():
+            times[n].append(_ms(fn, iters))
+    os.environ.pop("FF_MOE_SWIGLU_FUSED", None)
+    med = lambda v: sorted(v)[len(v) // 2]  # noqa: E731
+    rec = {"bench": "experts_swiglu", "tokens": B, "D": D, "H": H, "E": E, "k": k, "rows_per_expert": B * k // E}
+    for n, v in times.items():
+        rec[n + "_ms"] = round(med(v), 4)
+    for part in ("op", "fwd", "bwd"):
+        rec[part + "_fused_over_composed"] = round(med(times[part + "_fused"]) / med(times[part + "_composed"]), 4)
+    rec["op_fused_tflops"] = round(3 * 2 * 3 * B * k * D * H / med(times["op_fused"]) / 1e9, 1)
+    rec["all_ms"] = {n: [round(t, 4) for t in v] for n, v in times.items()}
+    emit(rec)
+
+
 def bench_step(B, D, H, E, k, reps, iters, emit):
     from flexflow_train_amd.core import AdamOptimizer, DataType, FFConfig, FFModel, LossType, MetricsType
 
@@ -127,7 +180,7 @@ def main():
     ap.add_argument("--hidden", type=int, default=4096)
     ap.add_argument("--experts", type=int, nargs="+", default=[8, 64])
     ap.add_argument("--topk", type=int, default=2)
-    ap.add_argument("--act", default="gelu")
+    ap.add_argument("--act", "--activation", default="gelu")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--no-step", action="store_true")
@@ -142,6 +195,10 @@ def main():
             out.write(line + "\n")
             out.flush()
 
+    if a.act == "swiglu":
+        for E in a.experts:
+            bench_swiglu(a.tokens, a.dim, a.hidden, E, a.topk, a.reps, a.iters, emit)
+        return
     for E in a.experts:
         bench_operator(a.tokens, a.dim, a.hidden, E, a.topk, a.act, a.reps, a.iters, emit)
     if not a.no_step:
