@@ -481,6 +481,16 @@ PYBIND11_MODULE(_ffkernels, m) {
                                     uintptr_t ws, uintptr_t st) {
     conv2d_grouped_wgrad(cshape(shp), groups, P(x), P(dy), F(dw), F(ws), S(st));
   });
+  m.def("dwconv_supported", [=](std::vector<int> shp, int dt) { return dwconv_supported(cshape(shp), dt); });
+  m.def("dwconv_wgrad_ws_floats", [=](std::vector<int> shp) { return dwconv_wgrad_ws_floats(cshape(shp)); });
+  m.def("dwconv_fwd", [=](int dt, std::vector<int> shp, uintptr_t x, uintptr_t w, uintptr_t bias, uintptr_t y,
+                          int act, uintptr_t st) {
+    dwconv_fwd(dt, cshape(shp), P(x), P(w), P(bias), P(y), act, S(st));
+  });
+  m.def("dwconv_dgrad", [=](int dt, std::vector<int> shp, uintptr_t dy, uintptr_t w, uintptr_t dx, float beta,
+                            uintptr_t st) { dwconv_dgrad(dt, cshape(shp), P(dy), P(w), P(dx), beta, S(st)); });
+  m.def("dwconv_wgrad", [=](int dt, std::vector<int> shp, uintptr_t x, uintptr_t dy, uintptr_t dw, uintptr_t ws,
+                            uintptr_t st) { dwconv_wgrad(dt, cshape(shp), P(x), P(dy), F(dw), F(ws), S(st)); });
   m.def("gemm_f32", [](uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias, uintptr_t pre, int64_t M, int64_t N,
                        int64_t K, int64_t lda, int64_t ldb, int64_t ldc, bool ta, bool tb, int act, float alpha,
                        float beta, int in_f32, int out_f32, uintptr_t st, int batch, int64_t sa, int64_t sb,

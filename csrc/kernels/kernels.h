@@ -480,6 +480,23 @@ int64_t conv2d_grouped_wgrad_ws_floats(const ConvShape& s, int groups);
 void conv2d_grouped_wgrad(const ConvShape& s, int groups, const void* x, const void* dy, float* dw, float* ws,
                           hipStream_t st);
 
+// ---- dwconv.hip: depthwise convolution (groups == C == K) as a direct
+// stencil, NHWC bf16 (C % 8 == 0) or fp32 (C % 4 == 0) activations, weight
+// [C][R][S] in the activations' type, filters of 1..7, fp32 arithmetic.
+// Anything dwconv_supported rejects throws std::invalid_argument.
+bool dwconv_supported(const ConvShape& s, int dtype);
+// y = act(conv + bias); act: none / relu / sigmoid / tanh; bias may be null
+void dwconv_fwd(int dtype, const ConvShape& s, const void* x, const void* w, const void* bias, void* y, int act,
+                hipStream_t st);
+// dx = conv_transpose(dy, w) + beta * dx
+void dwconv_dgrad(int dtype, const ConvShape& s, const void* dy, const void* w, void* dx, float beta,
+                  hipStream_t st);
+// dw (fp32 [C][R][S]) += wgrad; per-chunk partial sums in ws
+// (dwconv_wgrad_ws_floats(s) floats), summed in index order: no atomics
+int64_t dwconv_wgrad_ws_floats(const ConvShape& s);
+void dwconv_wgrad(int dtype, const ConvShape& s, const void* x, const void* dy, float* dw, float* ws,
+                  hipStream_t st);
+
 // ---- igemm32.hip: exact-fp32 MFMA (v_mfma_f32_32x32x2_f32) GEMM and
 // convolutions; fp32 or bf16 inputs (in_f32), fp32 accumulation.
 // GEMM: C = act(alpha op(A) op(B) + bias) [pre := pre-activation] (+ beta C),

@@ -2483,6 +2483,90 @@ def conv32_wgrad(x, dy, dw, R, S, stride=(1, 1), pad=(0, 0), dil=(1, 1), groups:
     STATS["conv32_wgrad"] += 1
 
 
+def _check_nhwc_dw(t: torch.Tensor, name: str, dtype):
+    if dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"{name}: depthwise kernels take bfloat16 or float32, got {dtype}")
+    _check_nhwc_any(t, name, dtype)
+    if t.data_ptr() % 16:
+        raise ValueError(f"{name}: data pointer must be 16-byte aligned")
+
+
+def _dwconv_geom(who, x_shape, w_shape, dtype, stride, pad, dil):
+    """Geometry list of a depthwise convolution: weight [C, R, S, 1] (the
+    physical [K][R][S][C/groups] with groups == C == K)."""
+    N, C, H, W = x_shape
+    if len(w_shape) != 4:
+        raise ValueError(f"{who}: weight must be [C, R, S, 1]")
+    K_, R, S, Cg = w_shape
+    if K_ != C:
+        raise ValueError(f"{who}: depthwise needs as many filters as channels (K={K_}, C={C})")
+    if Cg != 1:
+        raise ValueError(f"{who}: depthwise needs groups == C (weight has {Cg} channels per group)")
+    g = [int(N), int(H), int(W), int(C), int(K_), int(R), int(S), int(stride[0]), int(stride[1]),
+         int(pad[0]), int(pad[1]), int(dil[0]), int(dil[1])]
+    if not ext().dwconv_supported(g, DT_BF16 if dtype == torch.bfloat16 else DT_F32):
+        raise ValueError(f"{who}: unsupported depthwise shape {tuple(x_shape)} x {tuple(w_shape)} for {dtype} "
+                         "(C % 8 == 0 in bf16, C % 4 == 0 in fp32, filters of 1..7)")
+    return g
+
+
+def dwconv_fwd(x, w, bias=None, stride=(1, 1), pad=(0, 0), dil=(1, 1), act: str = "none"):
+    """Depthwise convolution (dwconv.hip): x [N,C,H,W] channels_last bf16 or
+    fp32, w [C,R,S,1] contiguous in x's dtype -> y = act(conv + bias),
+    channels_last."""
+    _check_nhwc_dw(x, "x", x.dtype)
+    _check(w, "w", x.dtype)
+    g = _dwconv_geom("dwconv_fwd", x.shape, w.shape, x.dtype, stride, pad, dil)
+    if act not in ("none", "relu", "sigmoid", "tanh"):
+        raise ValueError(f"dwconv_fwd: activation {act!r} is not none / relu / sigmoid / tanh")
+    C, R, S = w.shape[:3]
+    P, Q = conv_out_hw(x.shape[2], x.shape[3], R, S, *stride, *pad, *dil)
+    if bias is not None:
+        _check(bias, "bias", x.dtype, C)
+    y = torch.empty((x.shape[0], C, P, Q), device=x.device, dtype=x.dtype, memory_format=torch.channels_last)
+    ext().dwconv_fwd(_dt(x), g, _p(x), _p(w), _p(bias), _p(y), ACT_CODES[act], _stream())
+    STATS["dwconv_fwd"] += 1
+    return y
+
+
+def dwconv_dgrad(dy, w, x_shape, stride=(1, 1), pad=(0, 0), dil=(1, 1), out=None, beta: float = 0.0):
+    """dx of a depthwise convolution (``out`` with ``beta``: dx += / beta * dx)."""
+    _check_nhwc_dw(dy, "dy", dy.dtype)
+    _check(w, "w", dy.dtype)
+    g = _dwconv_geom("dwconv_dgrad", x_shape, w.shape, dy.dtype, stride, pad, dil)
+    C, R, S = w.shape[:3]
+    P, Q = conv_out_hw(x_shape[2], x_shape[3], R, S, *stride, *pad, *dil)
+    if tuple(dy.shape) != (x_shape[0], C, P, Q):
+        raise ValueError(f"dwconv_dgrad: dy {tuple(dy.shape)} / weight {tuple(w.shape)} do not match {tuple(x_shape)}")
+    if out is None:
+        out = torch.empty(tuple(x_shape), device=dy.device, dtype=dy.dtype, memory_format=torch.channels_last)
+        beta = 0.0
+    else:
+        _check_nhwc_dw(out, "dx", dy.dtype)
+        if tuple(out.shape) != tuple(x_shape):
+            raise ValueError("dwconv_dgrad: out has the wrong shape")
+    ext().dwconv_dgrad(_dt(dy), g, _p(dy), _p(w), _p(out), float(beta), _stream())
+    STATS["dwconv_dgrad"] += 1
+    return out
+
+
+def dwconv_wgrad(x, dy, dw, R, S, stride=(1, 1), pad=(0, 0), dil=(1, 1)):
+    """dw (fp32, contiguous, layout [C][R][S]) += depthwise weight gradient;
+    chunk partials summed in a fixed order (bit-reproducible)."""
+    _check_nhwc_dw(x, "x", x.dtype)
+    _check_nhwc_dw(dy, "dy", x.dtype)
+    C = x.shape[1]
+    g = _dwconv_geom("dwconv_wgrad", x.shape, (dy.shape[1], R, S, 1), x.dtype, stride, pad, dil)
+    P, Q = conv_out_hw(x.shape[2], x.shape[3], R, S, *stride, *pad, *dil)
+    if tuple(dy.shape) != (x.shape[0], C, P, Q):
+        raise ValueError("dwconv_wgrad: dy shape mismatch")
+    _check(dw, "dw", torch.float32, C * R * S)
+    # a stream-ordered temporary, so it is also valid inside a hipGraph capture
+    ws = torch.empty(ext().dwconv_wgrad_ws_floats(g), device=x.device, dtype=torch.float32)
+    ext().dwconv_wgrad(_dt(x), g, _p(x), _p(dy), _p(dw), _p(ws), _stream())
+    STATS["dwconv_wgrad"] += 1
+
+
 _BN_WS: Dict[tuple, torch.Tensor] = {}
 
 

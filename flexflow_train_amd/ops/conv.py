@@ -17,8 +17,10 @@ Backward = dgrad implicit GEMM + split-K wgrad accumulating in fp32 straight
 into the flat gradient buffer.  Inputs with fewer than 8 channels (the RGB
 stem) are zero-padded to 8.  bf16 grouped convolutions (ResNeXt) run on the
 same MFMA kernels as block-diagonal super-group convs (conv.hip
-group_plan); fp32 models on igemm32.hip; CPU tensors through PyTorch (the
-weight is viewed back to OIHW).
+group_plan); depthwise convolutions (groups == C == K, bf16 or fp32) on the
+direct stencil kernels of dwconv.hip (``FF_CONV_DEPTHWISE=0`` keeps them on
+the grouped / fp32 paths); fp32 models on igemm32.hip; CPU tensors through
+PyTorch (the weight is viewed back to OIHW).
 """
 from __future__ import annotations
 
@@ -174,6 +176,21 @@ class Conv2DOp(OpImpl):
         return any(groups % g == 0 and (g * cg) % 8 == 0 and (g * kg) % 8 == 0 for g in range(1, groups + 1))
 
     @staticmethod
+    def _native_depthwise(x, W, groups, act):
+        """One filter per channel (MobileNet, EfficientNet, ConvNeXt): the
+        direct stencil kernels (dwconv.hip), bf16 with channels in multiples
+        of 8 or fp32 in multiples of 4, filters up to 7x7.  Tested before the
+        grouped and fp32 paths; FF_CONV_DEPTHWISE=0 switches it off.  Forward
+        and dgrad always run there; the bf16 weight gradient mostly stays on
+        the grouped kernel (the rule is in _backward_depthwise)."""
+        if os.environ.get("FF_CONV_DEPTHWISE", "1") == "0":
+            return False
+        Kc, _, R, S = W.shape
+        return (x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and groups == x.shape[1] == Kc
+                and x.shape[1] % (8 if x.dtype == torch.bfloat16 else 4) == 0 and R <= 7 and S <= 7
+                and act in ("none", "relu", "sigmoid", "tanh") and K.use_hip(x))
+
+    @staticmethod
     def _native32(x, act):
         """fp32 models and grouped convolutions (ResNeXt): the exact-fp32 MFMA
         implicit GEMM (igemm32.hip), any channel count per group."""
@@ -227,6 +244,18 @@ class Conv2DOp(OpImpl):
                     and tuple(stride) == (1, 1) and C % 8 == 0):
                 bnsrc = getattr(x, "_ff_bn_bwd", None)   # set by the producing BatchNorm
             return [y], ("hip", xin, wp, y if act != "none" else None, tuple(x.shape), bnsrc)
+        if self._native_depthwise(x, W, groups, act):
+            wp = W.reshape(Kc, R, S, C)   # physical [C][R][S][1]
+            wp = (wp if wp.dtype == x.dtype else wp.to(x.dtype)).contiguous()
+            xin = x.contiguous(memory_format=torch.channels_last)
+            bias = None if b is None else b.to(x.dtype).contiguous()
+            y = K.dwconv_fwd(xin, wp, bias, stride, pad, act=act)
+            if ctx.extra.get("emit_bn_stats") and y.dtype == torch.bfloat16:
+                # a separate pass over y, as the pointwise GEMM route does
+                stats = torch.empty(2 * Kc, device=x.device, dtype=torch.float32)
+                K.bn_stats(y, stats, overwrite=True)
+                y._ff_bn_stats = stats
+            return [y], ("hipdw", xin, wp, y if act != "none" else None, tuple(x.shape))
         if self._native_grouped(x, W, groups, act):
             wp = W.reshape(Kc, R, S, C)   # physical [K][R][S][C/groups]
             wp = (wp if wp.dtype == torch.bfloat16 else wp.to(torch.bfloat16)).contiguous()
@@ -282,6 +311,8 @@ class Conv2DOp(OpImpl):
 
         if saved[0] == "hip32":
             return self._backward32(ctx, saved, grad_outputs, weight_grads, need_input_grad, stride, pad, act)
+        if saved[0] == "hipdw":
+            return self._backward_depthwise(ctx, saved, grad_outputs, weight_grads, need_input_grad, stride, pad, act)
         if saved[0] == "hipg":
             return self._backward_grouped(ctx, saved, grad_outputs, weight_grads, need_input_grad, stride, pad, act)
         _, xin, wp, y, xshape, bnsrc = saved
@@ -395,6 +426,51 @@ class Conv2DOp(OpImpl):
             K.conv2d_grouped_dgrad(dy, wexp, wshape, xshape, stride, pad, groups=groups, out=acc, beta=1.0)
             return [acc]
         return [K.conv2d_grouped_dgrad(dy, wexp, wshape, xshape, stride, pad, groups=groups)]
+
+    @staticmethod
+    def _backward_depthwise(ctx, saved, grad_outputs, weight_grads, need_input_grad, stride, pad, act):
+        _, xin, wp, y, xshape = saved
+        Kc, R, S, _ = wp.shape
+        dy = grad_outputs[0].to(xin.dtype).contiguous(memory_format=torch.channels_last)
+        if act == "relu":
+            dy = torch.where(y > 0, dy, torch.zeros((), device=dy.device, dtype=dy.dtype))
+        elif act in ("sigmoid", "tanh"):
+            yf = y.float()
+            d = yf * (1 - yf) if act == "sigmoid" else 1 - yf * yf
+            dy = (dy.float() * d).to(xin.dtype).contiguous(memory_format=torch.channels_last)
+        if len(weight_grads) > 1 and weight_grads[1] is not None:
+            d2 = dy.permute(0, 2, 3, 1).reshape(-1, Kc)
+            if Kc % 8 == 0:
+                K.colsum_act(d2, None, "none", weight_grads[1], write_dx=False)
+            else:
+                acc_grad(weight_grads[1], d2.float().sum(0))
+        dW = weight_grads[0]
+        if dW is not None:
+            # bf16 weight gradients stay on the super-group MFMA kernel, which was
+            # faster at five of the six measured shapes (profiles/dwconv.txt), except
+            # 7x7 filters on outputs of at most 14x14 (ConvNeXt stage 3: 0.088 against
+            # 0.107 ms); fp32 ones all take the stencil kernel (0.30 against 11.4 ms)
+            stencil = xin.dtype == torch.float32 or (R * S == 49 and dy.shape[2] * dy.shape[3] <= 196)
+
+            def wgrad(buf):
+                if stencil:
+                    K.dwconv_wgrad(xin, dy, buf, R, S, stride, pad)
+                else:
+                    K.conv2d_grouped_wgrad(xin, dy, buf, R, S, stride, pad, groups=Kc)
+            if dW.dtype == torch.float32 and dW.is_contiguous():
+                wgrad(dW.view(-1))
+            else:
+                tmp = torch.zeros(dW.numel(), device=dy.device, dtype=torch.float32)
+                wgrad(tmp)
+                acc_grad(dW, tmp.view(dW.shape))
+        if not need_input_grad[0]:
+            return [None]
+        acc = ctx.extra.get("grad_acc", [None])[0]
+        if (acc is not None and ctx.extra.get("halo") is None and acc.is_cuda and acc.dtype == xin.dtype
+                and tuple(acc.shape) == tuple(xshape) and acc.is_contiguous(memory_format=torch.channels_last)):
+            K.dwconv_dgrad(dy, wp, xshape, stride, pad, out=acc, beta=1.0)
+            return [acc]
+        return [K.dwconv_dgrad(dy, wp, xshape, stride, pad)]
 
     @staticmethod
     def _backward32(ctx, saved, grad_outputs, weight_grads, need_input_grad, stride, pad, act):
