@@ -233,6 +233,12 @@ int64_t attention_bwd_workspace(int B, int H, int Sq, int Sk, int D, bool causal
                                 bool varlen = false);
 int attention_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, int D, float scale, bool causal,
                   hipStream_t st, float* ws = nullptr);
+// ---- attention256.hip: the D = 256 kernels, reached through attention_fwd /
+// attention_bwd above.  kv_heads as there; every other optional field of
+// AttnTensors (dropout, kv_lens, q_lens, seg_offsets, bias, bias_grad, window,
+// dbq / dbk / dbv) is refused with std::invalid_argument before any launch.
+void attention256_fwd(const AttnTensors& t, int B, int H, int Sq, int Sk, float scale, bool causal, hipStream_t st);
+void attention256_bwd(const AttnTensors& t, int B, int H, int Sq, int Sk, float scale, bool causal, hipStream_t st);
 
 // ---- gemm.hip (bf16 MFMA GEMM with fused epilogues)
 // C[M,N] = act(alpha * op(A)[M,K] @ op(B)[K,N] + bias[N]) (+ beta*C)

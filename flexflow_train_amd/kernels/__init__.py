@@ -825,6 +825,23 @@ def _attn_window(window, causal, Sk, dropout_p=0.0, kv_lens=None, q_lens=None, s
     return W if W < Sk else 0
 
 
+def _attn_d256(D, dropout_p=0.0, kv_lens=None, q_lens=None, seg_lens=None, bias=None, window=None, dbias=None,
+               bias_grad=None):
+    """True if an attention call takes the D = 256 kernels (attention256.hip).
+    They serve causal and grouped-query calls and nothing else: every other
+    feature is refused here, by name, before anything is launched."""
+    if D != 256:
+        return False
+    for what, on in (("dropout_p", float(dropout_p) > 0.0), ("kv_lens", kv_lens is not None),
+                     ("q_lens", q_lens is not None), ("packed sequences (seg_lens)", seg_lens is not None),
+                     ("bias", bias is not None), ("bias_grad", bias_grad is not None),
+                     ("window", window is not None), ("the fused dbias", dbias is not None)):
+        if on:
+            raise ValueError(f"attention: head dim 256 cannot be combined with {what}")
+    STATS["attention_d256"] += 1
+    return True
+
+
 def attention_segment_offsets(seg_lens, T: int, max_seqlen: Optional[int] = None):
     """Clamped (start, len) of every segment of a packed batch: int32
     [N, M, 2] from ``seg_lens`` int32 [N, M], computed on the device (no host
@@ -946,14 +963,21 @@ def attention_fwd(q, k, v, causal=False, scale=None, out=None, dropout_p=0.0, se
     still read, unlike with ``kv_lens``: K / V under a mask must be finite.
     Needs Sk % 4 == 0, a 16-byte aligned base and batch / head / query strides
     that are 0 or multiples of 4; a bool bias is refused (convert it).
-    Excludes ``causal``, ``kv_lens`` / ``q_lens`` and ``seg_lens``."""
+    Excludes ``causal``, ``kv_lens`` / ``q_lens`` and ``seg_lens``.
+
+    Head dimension: D is 64, 128 or 256.  D = 256 (Gemma, GPT-J) runs kernels
+    of its own (attention256.hip) that serve ``causal``, grouped-query K / V,
+    cross-attention and strided views, and nothing else: ``dropout_p``,
+    ``kv_lens`` / ``q_lens``, ``seg_lens``, ``bias`` and ``window`` raise
+    ValueError at D = 256."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
-    if D not in (64, 128):
-        raise ValueError("attention: head dim must be 64 or 128")
+    if D not in (64, 128, 256):
+        raise ValueError("attention: head dim must be 64, 128 or 256")
+    d256 = _attn_d256(D, dropout_p, kv_lens, q_lens, seg_lens, bias, window)
     W = _attn_window(window, causal, Sk, dropout_p, kv_lens, q_lens, seg_lens, bias)
     Hkv = _attn_gqa(q, k, v, dropout_p, kv_lens, q_lens, seg_lens, bias)
-    if Hkv or W:
+    if Hkv or W or d256:
         if k.shape != (B, Sk, Hkv or H, D) or v.shape != (B, Sk, Hkv or H, D):
             raise ValueError("attention: q/k/v shape mismatch")
         if out is None:
@@ -1037,13 +1061,19 @@ def attention_bwd(q, k, v, o, lse, do, dq, dk, dv, causal=False, scale=None, dbi
 
     ``window``: the forward call's sliding window (always path 0, no
     ``dbias`` or ``bias_grad``); the dK/dV kernel ends a key block's query
-    loop at the last query that sees it.  Two calls give equal bits."""
+    loop at the last query that sees it.  Two calls give equal bits.
+
+    D = 256: the dQ and dK/dV kernels of attention256.hip (always path 0, no
+    workspace, no atomics: two calls give equal bits), with grouped-query
+    K / V as above; ``dbias``, ``bias_grad`` and everything the forward
+    refuses at D = 256 raise ValueError."""
     B, Sq, H, D = q.shape
     Sk = k.shape[1]
+    d256 = _attn_d256(D, dropout_p, kv_lens, q_lens, seg_lens, bias, window, dbias, bias_grad)
     W = _attn_window(window, causal, Sk, dropout_p, kv_lens, q_lens, seg_lens, bias, dbias, bias_grad)
     gview = _attn_bias_grad(bias_grad, bias, q, k, Sq, Sk)
     Hkv = _attn_gqa(q, k, v, dropout_p, kv_lens, q_lens, seg_lens, bias, dbias)
-    if Hkv or W:
+    if Hkv or W or d256:
         Hk = Hkv or H
         if k.shape != (B, Sk, Hk, D) or v.shape != (B, Sk, Hk, D):
             raise ValueError("attention: q/k/v shape mismatch")

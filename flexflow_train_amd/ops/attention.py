@@ -71,6 +71,16 @@ from .gemm import matmul, wgrad_matmul
 _FUSED_DBIAS = os.environ.get("FF_ATTN_FUSED_DBIAS", "0") == "1"
 
 
+def _flash_head_ok(D: int, plain: bool) -> bool:
+    """Whether the flash kernels serve head dimension ``D``.  64 and 128
+    always; 256 (attention256.hip) only for a ``plain`` call, one that uses
+    nothing those kernels refuse (dropout, lengths, packing, bias, window),
+    and unless FF_ATTN_D256=0 (read per call) sends it to the torch path."""
+    if D in (64, 128):
+        return True
+    return D == 256 and plain and os.environ.get("FF_ATTN_D256", "1") != "0"
+
+
 def _dims(ctx: OpContext, q, k, v, W):
     H_local = W.shape[-1] if W.dim() == 2 else None
     E = int(ctx.a("embed_dim"))
@@ -443,11 +453,14 @@ class MultiHeadAttentionOp(OpImpl):
             v = matmul(v_in.reshape(-1, Ev).contiguous(), ws["v"], bias=bv).view(B, Sk, Hl, vd)
             proj = (q, k, v)
         grp = ctx.extra.get("seq_group")
-        use_flash = (q.is_cuda and q.dtype == torch.bfloat16 and kd == vd and kd in (64, 128) and K.available())
         # dropout on the attention probabilities: training only.  drop = (p,
         # host seed, this forward's copy of the device step word), saved for
         # the backward; the mask is attention_dropout_mask(seed + step word)
         p_drop = float(ctx.a("dropout", 0.0) or 0.0) if ctx.training else 0.0
+        plain = (not (p_drop > 0 and K.attention_dropout_threshold(p_drop)) and lens is None and qlens is None
+                 and seg is None)
+        use_flash = (q.is_cuda and q.dtype == torch.bfloat16 and kd == vd and K.available()
+                     and _flash_head_ok(kd, plain))
         drop = None
         max_seqlen = (int(ctx.a("max_seqlen", 0) or 0) or Sq) if seg is not None else None
         seg_off = None
@@ -541,7 +554,8 @@ class MultiHeadAttentionOp(OpImpl):
                 dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
             fused_db = None
             # packed sequences: the column-sum pass below (tail rows of dQKV are zeros)
-            if _FUSED_DBIAS and seg is None and self_attn and db_in is not None and kd == vd \
+            # (and head dim 256: its kernels have no dbias epilogue)
+            if _FUSED_DBIAS and seg is None and kd != 256 and self_attn and db_in is not None and kd == vd \
                     and db_in.dtype == torch.float32 and db_in.is_contiguous():
                 dbf = db_in.reshape(-1)
                 n = Hl * kd
@@ -715,7 +729,8 @@ class ScaledDotProductAttentionOp(OpImpl):
         if p_drop > 0 and K.attention_dropout_threshold(p_drop):
             drop = (p_drop, _drop_seed(ctx), _drop_step(ctx, q.device))
         use_flash = (q.is_cuda and q.dtype == torch.bfloat16 and k.dtype == q.dtype and v.dtype == q.dtype
-                     and D in (64, 128) and v.shape[3] == D and K.available()
+                     and _flash_head_ok(D, mask is None and not drop and not window) and v.shape[3] == D
+                     and K.available()
                      and (mask is None or _flash_bias_ok(mask, Sk))
                      and not (window and drop))   # the WINDOW kernels have no dropout form
         if use_flash:

@@ -487,6 +487,64 @@ def gqa_ab(G, iters, rounds=5):
         print(json.dumps(rec), flush=True)
 
 
+def d256_ab(G, iters, rounds=5):
+    """--gqa G --head-dim 256: interleaved same-process timing at B = 4, S = 2048, causal, D = 256, with
+    H = 16 heads (G = 1, Gemma-7B-like) or H = 8 query heads over 8 / G K / V heads, three forms per round:
+      d256      the D = 256 kernels (attention256.hip);
+      fallback  ops.attention._torch_attention, the path of FF_ATTN_D256=0 and of the code before these
+                kernels: fp32 matmuls over [B, H, S, S], forward, and the operator's backward (the forward
+                again under autograd, then backward);
+      d128      the D = 128 kernels at 2 H heads (2 H / G K / V heads): the same flops, as a yardstick."""
+    import statistics
+
+    from flexflow_train_amd.ops.attention import _torch_attention
+    B, S, D, causal = 4, 2048, 256, True
+    H = 16 if G == 1 else 8
+    Hkv = H // G
+    g = torch.Generator(device="cuda").manual_seed(0)
+    mk = lambda h, d: torch.randn(B, S, h, d, device="cuda", dtype=torch.bfloat16, generator=g)  # noqa: E731
+    q, do, k, v = mk(H, D), mk(H, D), mk(Hkv, D), mk(Hkv, D)
+    q1, do1, k1, v1 = mk(2 * H, 128), mk(2 * H, 128), mk(2 * Hkv, 128), mk(2 * Hkv, 128)
+    sets = {"d256": (q, k, v, do), "d128": (q1, k1, v1, do1)}
+    scale = 1.0 / 16.0
+
+    def fb_fwd():
+        return _torch_attention(q, k.repeat_interleave(G, 2), v.repeat_interleave(G, 2), causal, scale)
+
+    def fb_bwd():
+        qf, kf, vf = (t.detach().float().requires_grad_(True) for t in (q, k, v))
+        _torch_attention(qf, kf.repeat_interleave(G, 2), vf.repeat_interleave(G, 2), causal, scale).float().backward(
+            do.float())
+        return qf.grad.to(q.dtype), kf.grad.to(q.dtype), vf.grad.to(q.dtype)
+
+    t = {}
+    for _ in range(rounds):
+        for tag in ("d256", "fallback", "d128"):
+            if tag == "fallback":
+                fwd, bwd, n = fb_fwd, fb_bwd, max(2, iters // 10)
+            else:
+                a, b, c, d = sets[tag]
+                o, lse = K.attention_fwd(a, b, c, causal=causal)
+                da, db, dc = torch.empty_like(a), torch.empty_like(b), torch.empty_like(c)
+                fwd = lambda: K.attention_fwd(a, b, c, causal=causal, out=o)  # noqa: E731
+                bwd = lambda: K.attention_bwd(a, b, c, o, lse, d, da, db, dc, causal=causal)  # noqa: E731
+                n = iters
+            t.setdefault(("fwd", tag), []).append(_time(fwd, n))
+            t.setdefault(("bwd", tag), []).append(_time(bwd, n))
+    fl = 4 * B * H * S * S * D * 0.5
+    rec = {"shape": f"b{B}-h{H}-hkv{Hkv}-d{D}-s{S}-causal", "iters": iters, "rounds": rounds}
+    for which, mul in (("fwd", 1.0), ("bwd", 2.5)):
+        for tag in ("d256", "fallback", "d128"):
+            xs = t[(which, tag)]
+            med = statistics.median(xs)
+            rec[f"{which}_ms_{tag}"] = round(med, 4)
+            rec[f"{which}_tflops_{tag}"] = round(mul * fl / med / 1e9, 1)
+            rec[f"{which}_spread_{tag}"] = round((max(xs) - min(xs)) / med, 4)
+        rec[f"{which}_d256_over_fallback"] = round(rec[f"{which}_ms_d256"] / rec[f"{which}_ms_fallback"], 3)
+        rec[f"{which}_d256_over_d128"] = round(rec[f"{which}_ms_d256"] / rec[f"{which}_ms_d128"], 3)
+    print(json.dumps(rec), flush=True)
+
+
 def window_ab(W, iters, rounds=5):
     """Interleaved same-process timing of sliding-window causal attention at
     S = 8192, B = 2, H = 32 query heads over 8 K / V heads, D in {128, 64}:
@@ -570,6 +628,10 @@ def main():
     if "--window" in sys.argv:        # sliding-window causal attention against global causal and the dense band mask
         return window_ab(int(sys.argv[sys.argv.index("--window") + 1]), 10)
     if "--gqa" in sys.argv:           # grouped-query K / V heads against the expanded and the H-head call
+        if "--head-dim" in sys.argv:  # --head-dim 256: the D = 256 kernels against the torch path and D = 128
+            if sys.argv[sys.argv.index("--head-dim") + 1] != "256":
+                raise SystemExit("--head-dim takes 256")
+            return d256_ab(int(sys.argv[sys.argv.index("--gqa") + 1]), 50)
         return gqa_ab(int(sys.argv[sys.argv.index("--gqa") + 1]), 200)
     if "--bias-grad" in sys.argv:      # gradient of a learned bias: the extra launch, and SDPA against the unfused chain
         return bias_grad_ab(30)

@@ -45,7 +45,7 @@ def _pybind_includes() -> list[str]:
 # and keep their flags, so that their code objects stay what was measured).
 # It costs swiglu.hip nothing: gemm_swiglu_kernel is the same 188 VGPRs / no
 # scratch either way, the element-wise kernels differ by a few VGPRs.
-_NO_PACKED_FP32 = ("swiglu.hip", "moe_swiglu.hip", "dwconv.hip")
+_NO_PACKED_FP32 = ("swiglu.hip", "moe_swiglu.hip", "dwconv.hip", "attention256.hip")
 
 
 def _hip_file_flags(src: str) -> list[str]:
